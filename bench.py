@@ -21,12 +21,18 @@ non-finite or any step was skipped prints no metric line and exits non-zero.
 --resolutions 256 512 alternates the resolution step by step (BASELINE config 4, /root/reference README.md:192-203:
 documented, never implemented there); every rank runs the same resolution in a given step.
 
-Rank 0 prints ONE JSON line.  `roofline` times the dominant kernel (the 192->192 3x3 implicit-GEMM
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the --steps steps and prints it; what else the
+benchmark measures runs only with --full: `roofline` times the dominant kernel (the 192->192 3x3 implicit-GEMM
 convolution of the 256x256 stages, tv_igemm_nt; one launch = 64 images) live with HIP events on the launch
 stream, `roofline.also` its weight gradient and the largest linear layer; `traffic` comes from the committed PMC
 summaries under profiles/ (labelled: not measured inside the run).  `cpu_baseline` times the fp32 CPU oracle (a
 port of the reference path, pinned to it by golden vectors) on a bounded sample: a micro-batch of 2
 images through the same train step, one untimed warm-up step + two timed steps, thread and core counts stated.
+
+--dump-outputs DIR writes what the last timed step computed, for output-for-output comparisons of two builds (same
+arguments, same seeded inputs): loss.npy and grad_norm.npy (float64, the step's loss and its gradient norm before clipping),
+param_sample.npy and grad_sample.npy (float32, the updated parameters and the step's gradients at up to 4096 seeded
+positions per parameter tensor, in named_parameters() order).
 
 Micro-batch: 128 images on a 288 GB device (peak 245 GiB; falls back to 64 if the first step runs out of memory),
 64 otherwise; `config.micro_batch` says which ran.  Started by torch.distributed.run (also with ONE rank) the step
@@ -181,6 +187,30 @@ def time_wgrad_kernel(mb: int, res: int, dev):
             "algorithmic_bytes_per_launch": 2 * mb * res * res * C * 2 + 9 * C * C * 4}
 
 
+DUMP_PER_TENSOR = 4096      # sampled positions per parameter tensor: Large 1.7 M, giant 3.1 M per array (<= 26 MB in all)
+
+
+def dump_outputs(model, loss: float, grad_norm: float, out_dir: str):
+    """The last timed step's results as DIR/<name>.npy: the loss and gradient norm in full, the updated parameters and the
+    step's gradients at fixed seeded positions (the same for every run with the same arguments)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator().manual_seed(0)
+    ps, gs = [], []
+    with torch.no_grad():
+        for _, p in model.named_parameters():
+            n = p.numel()
+            idx = (torch.arange(n) if n <= DUMP_PER_TENSOR else
+                   torch.randint(n, (DUMP_PER_TENSOR,), generator=g).sort().values).to(p.device)
+            ps.append(p.detach().reshape(-1).index_select(0, idx).float())
+            gs.append(p.grad.reshape(-1).index_select(0, idx).float() if p.grad is not None
+                      else torch.full((idx.numel(),), float("nan"), device=p.device))
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([loss], dtype=np.float64))
+    np.save(os.path.join(out_dir, "grad_norm.npy"), np.array([grad_norm], dtype=np.float64))
+    np.save(os.path.join(out_dir, "param_sample.npy"), torch.cat(ps).cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "grad_sample.npy"), torch.cat(gs).cpu().numpy().astype(np.float32))
+
+
 def cpu_baseline(variant: str, res: int, threads: int, lr: float, batch: int = 2, timed_steps: int = 2):
     """The oracle (CPU restatement of the reference path) on a bounded sample of the same workload, SURVEY 8d: a micro-batch
     of `batch` images through the SAME step as the GPU leg -- forward with the P/ clamps, L1 + 1e-8 KL with the logvar
@@ -262,7 +292,12 @@ def main():
                          "CNN stages only (2 instead of 4 saved full-resolution tensors per ResBlock), all = every block like the reference")
     ap.add_argument("--grad-exchange", choices=["fp32", "bf16"], default="fp32",
                     help="N > 1: gradient all-reduce in fp32 (4.2 GB per step, the reference's DDP) or with bf16 buckets (2.1 GB)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the dominant kernels (roofline) and the fp32 CPU baseline after the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (loss, gradient norm, sampled parameters "
+                         "and gradients)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--cpu-batch", type=int, default=2, help="images per step of the CPU baseline (SURVEY 8d: 2-4)")
     ap.add_argument("--dist-backend", choices=["auto", "nccl", "gloo", "none"], default="auto",
@@ -435,6 +470,8 @@ def main():
             dist.destroy_process_group()
         sys.exit(3)
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(model, final_loss, float(counters["grad_norm"]), args.dump_outputs)
     if rank == 0:
         ips = args.global_batch * args.steps / dt
         def gflop(r):
@@ -471,13 +508,14 @@ def main():
             out["flop_accounting"] = ("model_tflops = images/s x the REFERENCE's algorithmic FLOPs per image (SURVEY 8d: 2 MAC, 3x forward); the path "
                                       "executes fewer: exact reformulations (Conv-FFN tail on the composite W_out W3: -283 GF per Large image; "
                                       "polyphase up-convolutions: 4 taps for 9, ~-180 GF) -- DESIGN 4, 4.6")
-        log("timing the dominant kernel")
-        kmb = min(args.micro_batch, count, 64)     # ONE launch: 64 images (a 128-image micro-batch's 3.2 GB tensors go out as two launches of 64)
-        out["roofline"] = time_dominant_kernel(kmb, 256, dev)
-        # the dominant kernel BY TIME is the 3x3 convolution above (profiles/r04_rocprof_kernel_stats.csv: 17 % of the step);
-        # the largest weight-gradient kernel (9 %) is reported beside it
-        out["roofline"]["also"] = [time_wgrad_kernel(kmb, 256, dev), time_linear_kernel(kmb, dev)]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            log("timing the dominant kernel")
+            kmb = min(args.micro_batch, count, 64)     # ONE launch: 64 images (a 128-image micro-batch's 3.2 GB tensors go out as two launches of 64)
+            out["roofline"] = time_dominant_kernel(kmb, 256, dev)
+            # the dominant kernel BY TIME is the 3x3 convolution above (profiles/r04_rocprof_kernel_stats.csv: 17 % of the step);
+            # the largest weight-gradient kernel (9 %) is reported beside it
+            out["roofline"]["also"] = [time_wgrad_kernel(kmb, 256, dev), time_linear_kernel(kmb, dev)]
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("cpu baseline (oracle: 1 warm-up + 2 timed steps) ...")
             del model, ddp, opt
             torch.cuda.empty_cache()

@@ -891,3 +891,40 @@ def test_bench_two_rank_launch_as_the_driver_does_it():
     assert out["scaling"] == "strong" and out["unit"] == "images/sec" and out["value"] > 0
     assert out["skipped_steps"] == 0 and math.isfinite(out["final_loss"])
     assert out["config"]["global_batch"] == 8
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_outputs_and_full_adds_the_kernel_figures(tmp_path):
+    """A plain bench.py run times its steps and prints the result line without the roofline or the CPU baseline;
+    --dump-outputs DIR writes the last timed step's loss, gradient norm and sampled parameters / gradients (float npy,
+    finite, the loss equal to the line's final_loss); --full adds the roofline entries.  Tiny model at 64 x 64."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if not k.startswith("TV_")}
+    common = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+              "--variant", "tiny", "--res", "64", "--global-batch", "4", "--micro-batch", "2"]
+
+    def run(*extra):
+        r = subprocess.run(common + list(extra), cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                           text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0])
+
+    dump = str(tmp_path / "out")
+    out = run("--dump-outputs", dump)
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and len(out["losses"]) == 4
+    assert "roofline" not in out and "cpu_baseline" not in out
+    files = sorted(os.listdir(dump))
+    assert files == ["grad_norm.npy", "grad_sample.npy", "loss.npy", "param_sample.npy"]
+    arrs = {f[:-4]: np.load(os.path.join(dump, f)) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+    assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+    assert arrs["param_sample"].shape == arrs["grad_sample"].shape and arrs["grad_sample"].size > 0
+    assert abs(float(arrs["loss"][0]) - out["final_loss"]) <= 1e-5 * max(1.0, abs(out["final_loss"]))
+    assert float(arrs["grad_norm"][0]) > 0 and np.abs(arrs["grad_sample"]).max() > 0
+
+    full = run("--full", "--no-cpu-baseline")
+    assert full["roofline"]["achieved"] > 0 and len(full["roofline"]["also"]) == 2

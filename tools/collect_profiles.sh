@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/profiles_$R; mkdir -p $OUT
 P=gpurun_out/prof_raw; rm -rf $P; mkdir -p $P
 echo "[1] bench kernel stats"
-rocprofv3 --kernel-trace --stats --output-format csv -d $P/bench -o bench -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $P/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $P/bench -o bench -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline > $P/bench.log 2>&1
 cp $(find $P/bench -name "*kernel_stats.csv" | head -1) $OUT/${R}_rocprof_kernel_stats.csv
 echo "[2] dominant kernel alone"
 rocprofv3 --kernel-trace --stats --output-format csv -d $P/konly -o konly -- python3 bench.py --kernel-only --micro-batch 64 > $P/konly.log 2>&1
