@@ -1,0 +1,52 @@
+"""Drop-in for the reference's evaluation loop, R/evaluate.py:69-144 (`evaluate(model, dataloader, metrics, device)`).
+
+The reference copies every batch to the host and runs skimage one image at a time; here the per-image values come from
+:func:`transvae.metrics.reconstruction_metrics` on the device (the reference's definitions: inputs clipped to [0, 1],
+skimage's 7x7 SSIM, data_range 1), stay there while the loop runs and reach the host once, at the end.
+"""
+from __future__ import annotations
+
+from typing import Dict, Iterable, Sequence
+
+import numpy as np
+import torch
+
+from .metrics import reconstruction_metrics
+
+_KNOWN = ("psnr", "ssim", "mse")
+
+
+def evaluate(model: torch.nn.Module, dataloader: Iterable, metrics: Sequence[str] = ("psnr", "ssim"),
+             device="cuda", per_image: bool = False) -> Dict[str, Dict]:
+    """{metric: {"mean", "std", "median"}} over every image of `dataloader`, like R/evaluate.py.
+
+    `dataloader` yields `(images, labels)` pairs as in the reference (a bare image tensor is accepted too).  The model runs
+    in eval mode under no_grad as `model(images)`, so z is sampled as in the reference.  Metrics: "psnr", "ssim" and "mse"
+    (P/evaluate_transvae.py:134).  The statistics are NumPy's over the per-image values taken as float64 (`np.std` is the
+    population standard deviation).  "lpips" needs the external VGG network and raises ValueError.  per_image=True (not in
+    the reference) adds each metric's per-image values, in loader order, as a float64 array under "values".
+    """
+    metrics = tuple(metrics)
+    if "lpips" in metrics:
+        raise ValueError("evaluate (HIP path): the LPIPS term needs the external VGG network (lpips package) and is outside "
+                         "this build; drop 'lpips' from metrics and compute it with the reference's own module")
+    unknown = [m for m in metrics if m not in _KNOWN]
+    if unknown or not metrics:
+        raise ValueError(f"evaluate: unknown metrics {unknown} (expected a non-empty subset of {list(_KNOWN)})")
+    model.eval()
+    values = {m: [] for m in metrics}
+    with torch.no_grad():
+        for batch in dataloader:
+            images = batch[0] if isinstance(batch, (tuple, list)) else batch
+            images = images.to(device)
+            reconstruction = model(images)[0]
+            batch_values = reconstruction_metrics(reconstruction, images, ssim_window="skimage", transform="clip", data_range=1.0)
+            for m in metrics:
+                values[m].append(batch_values[m])
+    results = {}
+    for m in metrics:
+        v = torch.cat(values[m]).cpu().numpy().astype(np.float64) if values[m] else np.zeros(0)
+        results[m] = {"mean": float(np.mean(v)), "std": float(np.std(v)), "median": float(np.median(v))}
+        if per_image:
+            results[m]["values"] = v
+    return results

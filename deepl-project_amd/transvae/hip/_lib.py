@@ -20,6 +20,8 @@ SO_PATH = os.environ.get("TV_HIP_SO") or os.path.join(_HERE, "libtransvae_hip.so
 ACT_NONE, ACT_GELU, ACT_SILU = 0, 1, 2
 ACT_DERIV, ACT_SAVE_DERIV = 3, 16   # include/transvae_hip.h: saved tensor = act'(pre-activation)
 ACT_ADD = 4                         # aux_act of tv_igemm_nt_actgrad: out = conv + residual + aux (a second residual)
+SSIM_SKIMAGE, SSIM_BOX11 = 0, 1                 # tv_recon_metrics window kinds
+METRIC_NONE, METRIC_CLIP, METRIC_SIGMOID = 0, 1, 2   # tv_recon_metrics input transforms
 DERIVE_UP_FWD, DERIVE_UP_DGRAD, DERIVE_UP_WGRAD_FOLD, DERIVE_S2_PARITY = 1, 2, 3, 4   # tv_conv3x3_derived forms
 
 
@@ -76,6 +78,8 @@ SIGNATURES = {
     "tv_opt_adamw": (_I, [_P, _P, _I, _P, _F, _F, _F, _F, _F, _P]),
     "tv_opt_cast_shadows": (_I, [_P, _P, _I, _P]),
     "tv_pack_weight_multi": (_I, [_P, _I, _LL, _P]),
+    "tv_recon_metrics_partial_count": (_LL, [_I, _I, _I, _I, _I]),
+    "tv_recon_metrics": (_I, [_P, _P] + [_LL] * 8 + [_I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
 }
 
 _lib = None

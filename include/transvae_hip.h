@@ -292,6 +292,32 @@ int tv_vae_loss_l1_kl(const float* recon, const float* target, const float* mu, 
                       long long n_img, long long n_lat, float l1_weight, float kl_weight, float kl_denom,
                       int sigmoid, float logvar_lo, float logvar_hi, void* stream);
 
+/* Reconstruction metrics (evaluation, no gradient) -------------------------------------------------------------------------
+ * Per-image MSE / PSNR / SSIM of a batch of fp32 pairs recon, target [B, C, H, W], each addressed through its own element
+ * strides (n, c, h, w): NCHW-contiguous and channels_last tensors need no copy.  The input transform is applied first:
+ *   TV_METRIC_CLIP    clamp both to [0, 1]                       (R/evaluate.py:109-110)
+ *   TV_METRIC_SIGMOID sigmoid on recon only                      (P/evaluate_transvae.py:131)
+ * SSIM window kinds (C1 = (0.01 R)^2, C2 = (0.03 R)^2, R = data_range):
+ *   TV_SSIM_SKIMAGE   skimage structural_similarity defaults (R/evaluate.py:116-120): 7x7 uniform, scipy 'reflect' border,
+ *                     sample covariance (49/48), map cropped by 3 px, mean per channel then over channels; needs H, W >= 7
+ *   TV_SSIM_BOX11     P/evaluate_transvae.py:56-77: 11x11 uniform, zero border divided by 121, population covariance,
+ *                     mean over the whole map
+ * out[0][b] = mse, out[1][b] = 10 log10(R^2 / mse) (+inf when mse == 0), out[2][b] = ssim, fp32 [3][B].
+ * partials: tv_recon_metrics_partial_count(B, C, H, W, kind) floats of scratch (-1: bad arguments).  A stencil launch writes
+ * one partial pair per tile, a finalise launch adds an image's partials in a fixed order in fp64 (no atomics: bit-reproducible,
+ * independent of the rest of the batch). */
+#define TV_SSIM_SKIMAGE 0
+#define TV_SSIM_BOX11 1
+#define TV_METRIC_NONE 0
+#define TV_METRIC_CLIP 1
+#define TV_METRIC_SIGMOID 2
+long long tv_recon_metrics_partial_count(int B, int C, int H, int W, int kind);
+int tv_recon_metrics(const float* recon, const float* target,
+                     long long recon_sn, long long recon_sc, long long recon_sh, long long recon_sw,
+                     long long target_sn, long long target_sc, long long target_sh, long long target_sw,
+                     int B, int C, int H, int W, int kind, int transform, float data_range,
+                     float* partials, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
