@@ -592,7 +592,8 @@ def gemm_rows2(x1: torch.Tensor, x2: torch.Tensor, wb: torch.Tensor, c_out: int,
     T, K1 = x1.shape
     K2 = x2.shape[1]
     _require(x1.dtype == BF16 and x2.dtype == BF16 and x1.is_contiguous() and x2.is_contiguous() and x2.shape[0] == T and
-             tuple(wb.shape[-2:]) == (c_out, K1 + K2) or wb.numel() == c_out * (K1 + K2), "gemm_rows2: operand check failed")
+             wb.dtype == BF16 and wb.is_contiguous() and
+             (tuple(wb.shape[-2:]) == (c_out, K1 + K2) or wb.numel() == c_out * (K1 + K2)), "gemm_rows2: operand check failed")
     if K1 % 64 or K2 % 64 or _batch_chunks(T, (x1, x2, residual, aux)) is not None:
         return None
     d = _rows_desc(T, K1 + K2, c_out)

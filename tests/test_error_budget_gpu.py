@@ -1,0 +1,433 @@
+"""Error budget, GPU side: every kernel family against an fp64 reference of the same bf16 inputs, with the bound its row of
+the rounding contract implies (checks and references in tests/test_error_budget_host.py, whose mutation
+tests show that these bounds reject specific defects).  Inputs are built to reach where kernels go wrong: per-row scales
+of x over 2^-6..2^6, bias / residual that match or dominate the accumulator, ragged row tails, N edges, forced tiles;
+attention with a large common offset on v, spiked keys and rows whose max grows across the lazy-rescale threshold;
+GroupNorm with |mean| up to 100 std.  Every tuning hook a test sets is restored in a `finally`.
+"""
+import pytest
+import torch
+
+from test_error_budget_host import (
+    BF, F64, LSE_C, WGRAD_C, act_grad64, attn_bwd_emul, attn_bwd_exact, attn_exact, attn_fwd_emul, attn_inputs,
+    check_fp32, check_one_rounding, check_vs_emulation, conv64, deriv64, epilogue64, f32, gemm_inputs, gn_inputs,
+    gn_silu64, lse_terms, r16, wgrad64)
+
+pytestmark = pytest.mark.gpu
+
+
+def dev():
+    return torch.device("cuda:0")
+
+
+def report(tag, val):
+    print(f"[error-budget] {tag}: {val}")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# [W] hardware: does the bf16 MFMA's fp32 accumulation round to nearest?
+# ---------------------------------------------------------------------------------------------------------------------------
+def test_mfma_fp32_accumulation_rounds_to_nearest():
+    """Exact-input probe through the weight gradient (fp32 output): positive bf16 x, g, so every fp32 rounding of a growing
+    partial sum is a one-sided coin if the accumulation truncates (a bias of about -0.5 ulp per rounding, -40 in units of
+    2^-24 sum|g x| over these 8192 tokens) and unbiased if it rounds to nearest.  The fp64 reference is exact (products of
+    bf16 have 16 bits; 8192 of them fit in 53).  Asserts the mean signed error within +-2 units of 2^-24 sum|g x|."""
+    from transvae.hip import ops
+    g = torch.Generator().manual_seed(1)
+    T, K, N = 8192, 128, 128
+    x = r16(0.5 + 0.5 * torch.rand(T, K, generator=g, dtype=F64))
+    gy = r16(0.5 + 0.5 * torch.rand(T, N, generator=g, dtype=F64))
+    w = r16(torch.randn(N, K, generator=g, dtype=F64) * K ** -0.5)
+    xd = x.to(dev(), BF).requires_grad_(True)
+    wd = w.float().to(dev()).requires_grad_(True)
+    y = ops.linear(xd, wd)
+    y.backward(gy.to(dev(), BF))
+    torch.cuda.synchronize()
+    dw64, absd = wgrad64(x, gy)
+    e = (wd.grad.cpu().to(F64) - dw64) / (2.0 ** -24 * absd)
+    report("MFMA accumulation bias (units of 2^-24 sum|gx|)", f"mean {e.mean().item():+.3f} max {e.abs().max().item():.3f}")
+    assert abs(e.mean().item()) <= 2.0, e.mean().item()
+    check_fp32(wd.grad.cpu(), dw64, absd, WGRAD_C, "probe dw")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# [G] GEMM forward (linear) with every epilogue form, on the heuristic tile and on forced tiles
+# ---------------------------------------------------------------------------------------------------------------------------
+GEMM_SHAPES = [(2048 + 40, 64, 384), (2048 + 40, 192, 160), (2048 + 40, 1536, 384), (300, 192, 384)]
+TILE_CFGS = {"default": None, "256x256-8phase": (256, 256), "256x192-8phase": (256, 192), "nt-stores": "nt"}
+
+
+def _set_cfg(lib, cfg):
+    if cfg == "nt":
+        lib.tv_set_igemm_nt_threshold(0)
+    elif cfg is not None:
+        lib.tv_set_igemm_config(cfg[0], cfg[1], 0, 0)
+        lib.tv_set_igemm_persist(-2)
+
+
+def _reset_cfg(lib):
+    lib.tv_set_igemm_nt_threshold(64)
+    lib.tv_set_igemm_config(0, 0, 0, 0)
+    lib.tv_set_igemm_persist(-2)
+    lib.tv_set_igemm_persist(0)
+
+
+@pytest.mark.parametrize("cfg", list(TILE_CFGS))
+@pytest.mark.parametrize("M,K,N", GEMM_SHAPES)
+def test_gemm_forward_one_rounding(M, K, N, cfg):
+    """[G]: plain + bias, + residual, GELU with the saved derivative (TV_ACT_SAVE_DERIV), SiLU, and TV_ACT_ADD
+    (acc + residual + aux in one fp32 sum)"""
+    from transvae.hip import _lib as L, ops
+    lib = L.load()
+    x, w, b, res = gemm_inputs(M, K, N, seed=M + K + N)
+    aux = r16(res.flip(0))
+    acc, absdot = conv64(x, w, "linear")
+    xd, wd, bd, rd, ad = x.to(dev(), BF), w.float().to(dev()), b.float().to(dev()), res.to(dev(), BF), aux.to(dev(), BF)
+    wb = w.to(dev(), BF).contiguous()
+    try:
+        _set_cfg(lib, TILE_CFGS[cfg])
+        out = {
+            "plain": ops.conv_forward(xd, wd, bd, None, "linear", L.ACT_NONE, False)[0],
+            "residual": ops.conv_forward(xd, wd, bd, rd, "linear", L.ACT_NONE, False)[0],
+            "gelu+deriv": ops.conv_forward(xd, wd, bd, None, "linear", L.ACT_GELU, "deriv")[:2],
+            "silu": ops.conv_forward(xd, wd, bd, None, "linear", L.ACT_SILU, False)[0],
+            "act_add": ops.gemm_rows(xd, wb, N, residual=rd, aux=ad, aux_act=L.ACT_ADD),
+        }
+        torch.cuda.synchronize()
+    finally:
+        _reset_cfg(lib)
+    worst = {}
+    y64, sl, _ = epilogue64(acc, absdot, b)
+    worst["plain"] = check_one_rounding(out["plain"].cpu(), y64, sl, "plain")
+    y64, sl, _ = epilogue64(acc, absdot, b, res)
+    worst["residual"] = check_one_rounding(out["residual"].cpu(), y64, sl, "residual")
+    y64, sl, z = epilogue64(acc, absdot, b, None, "gelu")
+    worst["gelu"] = check_one_rounding(out["gelu+deriv"][0].cpu(), y64, sl, "gelu")
+    d64, dsl = deriv64(z, absdot, b, "gelu")
+    worst["gelu'"] = check_one_rounding(out["gelu+deriv"][1].cpu(), d64, dsl, "saved gelu'")
+    y64, sl, _ = epilogue64(acc, absdot, b, None, "silu")
+    worst["silu"] = check_one_rounding(out["silu"].cpu(), y64, sl, "silu")
+    y64, sl, _ = epilogue64(acc, absdot, None, res + aux)
+    sl = sl + 2.0 ** -24 * aux.abs()
+    worst["act_add"] = check_one_rounding(out["act_add"].cpu(), y64, sl, "acc + residual + aux")
+    report(f"[G] linear {M}x{K}x{N} {cfg} (ratio, max ulps, bias)",
+           {k: tuple(round(v, 3) for v in t) for k, t in worst.items()})
+
+
+def test_gemm_rows2_against_fp64_of_the_concatenation():
+    """[G]/[D]: the two-source loop against fp64 of [x1 | x2] w^T, forward (bias + residual) and data-gradient
+    (saved-derivative multiply) forms, 256-row tiles, ragged rows"""
+    from transvae.hip import _lib as L, ops
+    lib = L.load()
+    T, K1, K2, N = 2048 + 72, 1536, 384, 768
+    x, w, b, res = gemm_inputs(T, K1 + K2, N, seed=77)
+    der = r16(torch.rand(T, N, generator=torch.Generator().manual_seed(3), dtype=F64))
+    x1, x2 = x[:, :K1].contiguous(), x[:, K1:].contiguous()
+    acc, absdot = conv64(x, w, "linear")
+    d = lambda t: t.to(dev(), BF).contiguous()
+    try:
+        for bn in (256, 192):
+            lib.tv_set_igemm_config(256, bn, 0, 0)
+            y = ops.gemm_rows2(d(x1), d(x2), d(w), N, bias=b.float().to(dev()), residual=d(res))
+            dx = ops.gemm_rows2(d(x1), d(x2), d(w), N, aux=d(der), aux_act=L.ACT_DERIV)
+            assert y is not None and dx is not None
+            y64, sl, _ = epilogue64(acc, absdot, b, res)
+            r1 = check_one_rounding(y.cpu(), y64, sl, f"rows2 bias+residual bn={bn}")
+            r2 = check_one_rounding(dx.cpu(), acc * der, 2.0 ** -20 * absdot * der, f"rows2 x deriv bn={bn}")
+            report(f"[G] rows2 bn={bn}", (tuple(round(v, 3) for v in r1), tuple(round(v, 3) for v in r2)))
+    finally:
+        lib.tv_set_igemm_config(0, 0, 0, 0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# [G] / [D] / [W] convolutions: forward, data gradient, weight gradient
+# ---------------------------------------------------------------------------------------------------------------------------
+def conv_inputs(mode, B, H, W, Cin, Cout, seed, exact_taps=False):
+    """x with per-image / per-channel scales; w with per-output-channel scales.  exact_taps: w = (integer in [-8, 8]) 2^-s,
+    so the polyphase / adjoint operands (sums of up to four taps, ops._up_fwd_weight / _up_dgrad_weight) are exact in
+    bf16 and the operand the kernel consumes equals w"""
+    g = torch.Generator().manual_seed(seed)
+    kh = {"c3s1": 3, "c3s2": 3, "c3up": 3, "unshuf": 2, "shuf": 1}[mode]
+    co = 4 * Cout if mode == "shuf" else Cout
+    xs = torch.exp2(torch.randint(-4, 5, (B, 1, 1, Cin), generator=g).to(F64))
+    x = r16(torch.randn(B, H, W, Cin, generator=g, dtype=F64) * xs)
+    cs = torch.exp2(torch.randint(-2, 3, (co, 1, 1, 1), generator=g).to(F64))
+    if exact_taps:
+        w = torch.randint(-8, 9, (co, kh, kh, Cin), generator=g).to(F64) * 2.0 ** -7 * cs
+    else:
+        w = r16(torch.randn(co, kh, kh, Cin, generator=g, dtype=F64) * cs * (kh * kh * Cin) ** -0.5)
+    b = f32(torch.randn(co if mode != "shuf" else co, generator=g, dtype=F64) * cs.flatten() * 0.5)
+    return x, w, b
+
+
+def conv_grads64(x, w, gy, mode):
+    """fp64 (dx, sum|w gy| per dx element, dw, sum|x gy| per dw element) through autograd of conv64"""
+    def vjp(xx, ww, gg):
+        xx = xx.clone().requires_grad_(True)
+        ww = ww.clone().requires_grad_(True)
+        y, _ = conv64(xx, ww, mode)
+        y.backward(gg)
+        return xx.grad, ww.grad
+    dx, dw = vjp(x.to(F64), w.to(F64), gy.to(F64))
+    adx, adw = vjp(x.to(F64).abs(), w.to(F64).abs(), gy.to(F64).abs())
+    return dx, adx, dw, adw
+
+
+CONV_CASES = [
+    # mode, B, H, W, Cin, Cout, halo
+    ("c3s1", 2, 32, 40, 64, 192, 1),
+    ("c3s1", 2, 32, 40, 64, 192, 0),
+    ("c3s1", 3, 16, 16, 192, 160, 1),
+    ("c3s2", 2, 32, 24, 96, 128, 1),
+    ("c3up", 2, 16, 12, 128, 64, 1),
+    ("unshuf", 2, 16, 24, 64, 128, 1),
+    ("shuf", 2, 12, 10, 128, 64, 1),
+]
+
+
+@pytest.mark.parametrize("case", CONV_CASES, ids=[f"{c[0]}-{c[1]}x{c[2]}x{c[3]}x{c[4]}-{c[5]}-halo{c[6]}" for c in CONV_CASES])
+def test_conv_forward_dgrad_wgrad(case):
+    """[G] forward with SiLU + residual and with the saved SiLU derivative; [D] data gradient plain, x saved derivative
+    (TV_ACT_DERIV), x act' of a saved pre-activation (its bf16 copy) and (acc + residual) x derivative; [W] weight and
+    bias gradient (fp32, run twice: split-K atomics reorder the sums)"""
+    from transvae.hip import _lib as L, ops
+    mode, B, H, W, Cin, Cout, halo = case
+    lib = L.load()
+    x, w, b = conv_inputs(mode, B, H, W, Cin, Cout, seed=B * H + Cin, exact_taps=(mode == "c3up"))
+    acc, absdot = conv64(x, w, mode)
+    bb = b if mode != "shuf" else None
+    g = torch.Generator().manual_seed(9)
+    res = r16(acc * (torch.randn(acc.shape, generator=g, dtype=F64) * 0.5 - 1))     # same magnitude, partly cancelling
+    gz = r16(torch.randn(acc.shape, generator=g, dtype=F64) * torch.exp2(torch.randint(-3, 4, (1, 1, 1, acc.shape[-1]), generator=g).to(F64)))
+    der = r16(torch.rand(x.shape, generator=g, dtype=F64))
+    pre = r16(torch.randn(x.shape, generator=g, dtype=F64) * 2)
+    gres = r16(torch.randn(x.shape, generator=g, dtype=F64))
+    xd, wd = x.to(dev(), BF), w.float().to(dev())
+    bd = bb.float().to(dev()) if bb is not None else None
+    try:
+        lib.tv_set_igemm_halo(halo)
+        y_res = ops.conv_forward(xd, wd, bd, res.to(dev(), BF), mode, L.ACT_SILU, False)[0]
+        y_d, sd = ops.conv_forward(xd, wd, bd, None, mode, L.ACT_SILU, "deriv")[:2]
+        geo = ops._Geo(mode, xd, wd)
+        gzd = gz.to(dev(), BF)
+        dx = ops.conv_dgrad(geo, wd, gzd, x.shape)
+        dx_der = ops.conv_dgrad(geo, wd, gzd, x.shape, aux=der.to(dev(), BF), aux_act=L.ACT_DERIV)
+        dx_pre = ops.conv_dgrad(geo, wd, gzd, x.shape, aux=pre.to(dev(), BF), aux_act=L.ACT_GELU)
+        dx_res = ops.conv_dgrad(geo, wd, gzd, x.shape, residual=gres.to(dev(), BF), aux=der.to(dev(), BF), aux_act=L.ACT_DERIV)
+        dws = []
+        for _ in range(2):
+            xr = xd.clone().requires_grad_(True)
+            wr = wd.clone().requires_grad_(True)
+            br = bd.clone().requires_grad_(True) if bd is not None else None
+            ops.conv(xr, wr, br, None, mode=mode).backward(gzd)
+            dws.append((wr.grad.cpu(), None if br is None else br.grad.cpu()))
+        torch.cuda.synchronize()
+    finally:
+        lib.tv_set_igemm_halo(1)
+    out = {}
+    y64, sl, z = epilogue64(acc, absdot, bb, res, "silu")
+    out["silu+res"] = check_one_rounding(y_res.cpu(), y64, sl, "forward silu + residual")
+    y64, sl, z = epilogue64(acc, absdot, bb, None, "silu")
+    out["silu(saved)"] = check_one_rounding(y_d.cpu(), y64, sl, "forward silu, derivative saved")
+    d64, dsl = deriv64(z, absdot, bb, "silu")
+    out["silu'"] = check_one_rounding(sd.cpu(), d64, dsl, "saved silu'")
+    dx64, adx, dw64, adw = conv_grads64(x, w, gz, mode)
+    e = 2.0 ** -20 * adx
+    out["dgrad"] = check_one_rounding(dx.cpu(), dx64, e, "dgrad")
+    out["dgrad*deriv"] = check_one_rounding(dx_der.cpu(), dx64 * der, e * der, "dgrad x deriv")
+    gp = act_grad64(pre, "gelu")
+    out["dgrad*gelu'(pre)"] = check_one_rounding(dx_pre.cpu(), dx64 * gp, e * gp.abs() + 2.0 ** -20 * (1 + pre.abs()) * dx64.abs(),
+                                                 "dgrad x gelu'(saved pre-activation)")
+    out["(dgrad+res)*deriv"] = check_one_rounding(dx_res.cpu(), (dx64 + gres) * der, (e + 2.0 ** -24 * gres.abs()) * der,
+                                                  "(dgrad + residual) x deriv")
+    dwk, adwk = dw64, adw          # (autograd of conv64 returns the gradient in w's own [Cout, KH, KW, Cin] layout)
+    db64, adb = gz.to(F64).sum((0, 1, 2)), gz.to(F64).abs().sum((0, 1, 2))
+    for i, (dw, db) in enumerate(dws):
+        out[f"dw#{i}"] = (check_fp32(dw, dwk, adwk, WGRAD_C, f"wgrad run {i}"),)
+        if db is not None:
+            out[f"db#{i}"] = (check_fp32(db, db64, adb, WGRAD_C, f"bias grad run {i}"),)
+    report(f"[G/D/W] {case}", {k: tuple(round(v, 3) for v in t) for k, t in out.items()})
+
+
+@pytest.mark.parametrize("W", [8, 16, 32, 64, 128])
+def test_wgrad_widths(W):
+    """[W] the kx3 weight gradient over image widths 8 .. 128 (split-K; each run twice: atomics reorder the sums) and the
+    single-tap one (a 1x1 linear layer over the same pixels)"""
+    from transvae.hip import ops
+    g = torch.Generator().manual_seed(W)
+    B, H, C, Co = 4, 64 if W <= 32 else 16, 128, 192
+    x = r16(torch.randn(B, H, W, C, generator=g, dtype=F64))
+    w = r16(torch.randn(Co, 3, 3, C, generator=g, dtype=F64) * (9 * C) ** -0.5)
+    gz = r16(torch.randn(B, H, W, Co, generator=g, dtype=F64))
+    _, _, dw64, adw = conv_grads64(x, w, gz, "c3s1")
+    w1 = r16(torch.randn(Co, C, generator=g, dtype=F64) * C ** -0.5)
+    dl64, adl = wgrad64(x, gz)
+    worst = []
+    for _ in range(2):
+        wr = w.float().to(dev()).requires_grad_(True)
+        ops.conv(x.to(dev(), BF), wr, None, None, mode="c3s1").backward(gz.to(dev(), BF))
+        wl = w1.float().to(dev()).requires_grad_(True)
+        ops.linear(x.reshape(-1, C).to(dev(), BF), wl).backward(gz.reshape(-1, Co).to(dev(), BF))
+        torch.cuda.synchronize()
+        worst.append(check_fp32(wr.grad.cpu(), dw64, adw, WGRAD_C, f"kx3 dw W={W}"))
+        worst.append(check_fp32(wl.grad.cpu(), dl64, adl, WGRAD_C, f"one-tap dw W={W}"))
+    report(f"[W] W={W} max ratio", round(max(worst), 3))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# [A] attention
+# ---------------------------------------------------------------------------------------------------------------------------
+def _rope_table(N, seed):
+    g = torch.Generator().manual_seed(seed)
+    ang = torch.rand(N, 32, generator=g) * 6.28
+    tab = torch.stack([torch.cos(ang), torch.sin(ang), torch.cos(ang * 0.5), torch.sin(ang * 0.5)], 1)
+    return tab.contiguous()
+
+
+def _sample_groups(N, n):
+    """32-row waves to emulate: all of them up to n, else the first, the last (ragged) and evenly spread others"""
+    G = -(-N // 32)
+    if G <= n:
+        return list(range(G))
+    return sorted(set([0, G - 1] + [int(i * (G - 1) / (n - 1)) for i in range(n)]))
+
+
+ATTN_CASES = [
+    # N, heads, rope, design
+    (16, 2, False, "plain"),
+    (300, 2, True, "offset-v"),
+    (300, 2, False, "spiked"),
+    (512, 1, False, "lazy-rows"),
+    (2160, 1, False, "spiked"),
+    (4096, 1, True, "plain"),
+    (4096, 1, False, "offset-v"),
+]
+
+
+@pytest.mark.parametrize("case", ATTN_CASES, ids=[f"N{c[0]}-h{c[1]}-{'rope' if c[2] else 'norope'}-{c[3]}" for c in ATTN_CASES])
+def test_attention_against_emulation(case):
+    """[A] o and lse of the forward (32-query kernel below 2048 tokens, 64-query kernel from there: key blocks of 64 / 32 in
+    the lazy policy), delta, and dq / dk / dv, per (image, head) slice"""
+    from transvae.hip import _lib as L
+    import ctypes as C
+    N, heads, rope, design = case
+    lib = L.load()
+    Cc = heads * 64
+    sl = []
+    for h in range(heads):
+        kw = dict(seed=N + h)
+        if design == "offset-v":
+            kw["v_offset"] = 4.0
+        if design == "spiked":
+            kw["spikes"] = ((N // 2 + 3, 5, 6.0), (N - 70, 40, 9.0), (N - 1, 130, 12.0), (200, 131, 4.0))
+        if design == "lazy-rows":
+            kw["lazy_rows"] = [(qi, 5 * 64 + 7 + qi % 30, 8.4 if qi % 2 else 7.6) for qi in range(64, 96, 5)]
+        sl.append(attn_inputs(N, **kw))
+    qkv = torch.cat([torch.cat([s[i] for s in sl], 1) for i in range(3)], 1)[None].float()       # [1, N, 3C]
+    qkv_d = qkv.to(dev(), BF).contiguous()
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    if rope:
+        tab = _rope_table(N, 3).to(dev())
+        L.check(lib.tv_rope_qk(p(qkv_d), p(tab), 1, N, heads, 0, stream), "tv_rope_qk")
+    o = torch.empty(1, N, Cc, dtype=BF, device=dev())
+    lse = torch.empty(1, heads, N, dtype=torch.float32, device=dev())
+    L.check(lib.tv_attn_fwd(p(qkv_d), p(o), p(lse), 1, N, heads, 0.125, stream), "tv_attn_fwd")
+    g = torch.Generator().manual_seed(N)
+    do = r16(torch.randn(1, N, Cc, generator=g, dtype=F64))
+    do_d = do.to(dev(), BF)
+    delta = torch.empty(2, 1, heads, N, dtype=torch.float32, device=dev())
+    dqkv = torch.empty_like(qkv_d)
+    L.check(lib.tv_attn_bwd(p(qkv_d), p(o), p(do_d), p(lse), p(delta), None, p(dqkv), 1, N, heads, 0.125, stream), "tv_attn_bwd")
+    torch.cuda.synchronize()
+    qkv_h, o_h, lse_h, dl_h, dqkv_h = qkv_d.cpu().to(F64)[0], o.cpu().to(F64)[0], lse.cpu().to(F64)[0], delta.cpu().to(F64), dqkv.cpu().to(F64)[0]
+    kb = 32 if N >= 2048 else 64
+    res = {}
+    for h in range(heads):
+        cs = slice(h * 64, h * 64 + 64)
+        q, k, v = qkv_h[:, cs], qkv_h[:, Cc + h * 64:Cc + h * 64 + 64], qkv_h[:, 2 * Cc + h * 64:2 * Cc + h * 64 + 64]
+        o_ex, lse_ex = attn_exact(q, k, v, 0.125)
+        grp = _sample_groups(N, 12)
+        rows = torch.cat([torch.arange(g0 * 32, min(N, g0 * 32 + 32)) for g0 in grp])
+        o_e = torch.empty(0, 64, dtype=F64)
+        for g0 in grp:
+            r0, r1 = g0 * 32, min(N, g0 * 32 + 32)
+            # a wave's rows are independent of the other waves: emulate it on its own (keys: all of them)
+            oo, _ = attn_fwd_emul(q[r0:r1], k, v, 0.125, kblock=kb, group=32)
+            o_e = torch.cat([o_e, oo])
+        res[f"o h{h}"] = check_vs_emulation(o_h[rows, cs], o_e, o_ex[rows], f"o head {h}")
+        res[f"lse h{h}"] = (check_fp32(lse_h[h], lse_ex, lse_terms(q, k, lse_ex, 0.125), LSE_C, f"lse head {h}"),)
+        dox = do[0, :, cs].to(F64)
+        d64 = (dox * o_h[:, cs]).sum(1)
+        res[f"delta h{h}"] = (check_fp32(-dl_h[0, 0, h], d64, (dox * o_h[:, cs]).abs().sum(1), 16.0, f"delta head {h}"),)
+        ex = attn_bwd_exact(q, k, v, o_h[:, cs], dox, lse_h[h], 0.125)
+        em = attn_bwd_emul(q, k, v, o_h[:, cs], dox, lse_h[h], 0.125)
+        got = (dqkv_h[:, cs], dqkv_h[:, Cc + h * 64:Cc + h * 64 + 64], dqkv_h[:, 2 * Cc + h * 64:2 * Cc + h * 64 + 64])
+        # (with RoPE: q, k are the rotated bf16 values the kernels read back from qkv; dq, dk are in that frame -- ops applies
+        # the adjoint rotation after tv_attn_bwd)
+        for i, nm in enumerate(("dq", "dk", "dv")):
+            res[f"{nm} h{h}"] = check_vs_emulation(got[i], em[i], ex[i], f"{nm} head {h}")
+    report(f"[A] {case} (relL2 ratio, max ratio)", {k: tuple(round(v, 3) for v in t) for k, t in res.items()})
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# [N] GroupNorm + SiLU and the row norms
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("B,HW,C,G", [(2, 1024, 128, 32), (3, 640, 192, 32)])
+def test_groupnorm_silu(B, HW, C, G):
+    """[N] forward: one rounding of silu(x sc + sh) (z in fp32 from x and the fp32 scale / shift); backward: dx one
+    rounding, dgamma / dbeta fp32 sums; means up to 100 std, stds 1e-2 .. 1e2"""
+    from transvae.hip import ops
+    x, gamma, beta = gn_inputs(B, HW, C, G, seed=B * C)
+    H = 32
+    gy = r16(torch.randn(B, HW, C, generator=torch.Generator().manual_seed(2), dtype=F64))
+    xd = x.view(B, H, HW // H, C).to(dev(), BF).contiguous().requires_grad_(True)
+    gd = gamma.float().to(dev()).requires_grad_(True)
+    bd = beta.float().to(dev()).requires_grad_(True)
+    y = ops.group_norm_silu(xd, gd, bd, G)
+    y.backward(gy.view(B, H, HW // H, C).to(dev(), BF))
+    torch.cuda.synchronize()
+    y64, slack, z, xh, rstd = gn_silu64(x, gamma, beta, G)
+    out = {"y": check_one_rounding(y.cpu().view(B, HW, C), y64, slack, "GroupNorm + SiLU forward")}
+    # backward in fp64: g' = gy silu'(z); dx = rstd gamma (g' - mean g' - xhat mean(g' xhat)) per group
+    gp = gy * act_grad64(z, "silu")
+    gpg = (gp * gamma).view(B, HW, G, C // G)
+    xhg = xh.view(B, HW, G, C // G)
+    r = rstd.view(B, 1, G, 1)
+    m1 = gpg.mean((1, 3), keepdim=True)
+    m2 = (gpg * xhg).mean((1, 3), keepdim=True)
+    dx64 = (r * (gpg - m1 - xhg * m2)).view(B, HW, C)
+    mu_r = (x.view(B, HW, G, C // G).mean((1, 3), keepdim=True) * r).abs()
+    # fp32 z (2^-22 (|x sc| + |sh|)) moves silu'; the sums and the final fma chain: 2^-19 of the terms' magnitudes
+    terms = (r * (gpg.abs() + gpg.abs().mean((1, 3), keepdim=True) + xhg.abs() * (gpg * xhg).abs().mean((1, 3), keepdim=True))).view(B, HW, C)
+    dsl = 2.0 ** -19 * terms * (1 + mu_r.expand(B, HW, G, C // G).reshape(B, HW, C)) + 2.0 ** -20 * dx64.abs()
+    out["dx"] = check_one_rounding(xd.grad.cpu().view(B, HW, C), dx64, dsl, "GroupNorm + SiLU dx")
+    dg64 = (gp * xh).sum((0, 1))
+    db64 = gp.sum((0, 1))
+    xh_err = (mu_r.expand(B, HW, G, C // G).reshape(B, HW, C) + xh.abs() + 1)   # xhat to 2^-22 of |x| rstd
+    out["dgamma"] = (check_fp32(gd.grad.cpu(), dg64, (gp.abs() * xh_err).sum((0, 1)), 64.0, "dgamma"),)
+    out["dbeta"] = (check_fp32(bd.grad.cpu(), db64, (gp.abs() * xh_err).sum((0, 1)), 64.0, "dbeta"),)
+    report(f"[N] GroupNorm {B}x{HW}x{C}/{G}", {k: tuple(round(v, 3) for v in t) for k, t in out.items()})
+
+
+@pytest.mark.parametrize("T,Cc", [(300, 384), (2048 + 40, 768), (40, 1536)])
+def test_rms_hat(T, Cc):
+    """[N] rms_hat: y = x rsqrt(mean x^2 + eps) one rounding (2^-20 |y| for the fp32 sum and rsqrt); dx = r (g - xhat
+    mean(g xhat)) one rounding (2^-19 of the terms)"""
+    from transvae.hip import ops
+    g = torch.Generator().manual_seed(T)
+    rs = torch.exp2(torch.randint(-6, 7, (T, 1), generator=g).to(F64))
+    x = r16(torch.randn(T, Cc, generator=g, dtype=F64) * rs)
+    gy = r16(torch.randn(T, Cc, generator=g, dtype=F64))
+    xd = x.to(dev(), BF).requires_grad_(True)
+    y = ops.rms_hat(xd)
+    y.backward(gy.to(dev(), BF))
+    torch.cuda.synchronize()
+    r = 1.0 / torch.sqrt((x * x).mean(1, keepdim=True) + 1e-6)
+    y64 = x * r
+    out = {"y": check_one_rounding(y.cpu(), y64, 2.0 ** -20 * y64.abs(), "rms_hat")}
+    m = (gy * y64).mean(1, keepdim=True)
+    dx64 = r * (gy - y64 * m)
+    terms = r * (gy.abs() + y64.abs() * (gy * y64).abs().mean(1, keepdim=True))
+    out["dx"] = check_one_rounding(xd.grad.cpu(), dx64, 2.0 ** -19 * terms, "rms_hat dx")
+    report(f"[N] rms_hat {T}x{Cc}", {k: tuple(round(v, 3) for v in t) for k, t in out.items()})
