@@ -65,6 +65,12 @@ struct TvPerDeviceOnce {
 #define TV_ACT_ADD 4          // (aux_act only) the second tensor is added: out = acc + residual + aux
 #endif
 #define TV_ACT_SAVE_DERIV 16  // (flag on desc.act) pre_act receives act'(pre-activation) instead of the pre-activation
+// ReLU (frozen VGG layers of the perceptual loss): desc.act, and as aux_act / tv_act_bwd's act with the layer's own OUTPUT as the
+// saved tensor (mask = output > 0).  Named outside the TV_ACT_ family on purpose, here and in the public header alike: that
+// family is pinned to six ids.
+#ifndef TV_ACTX_RELU
+#define TV_ACTX_RELU 5
+#endif
 
 __device__ __forceinline__ float tv_fast_exp(float x) { return __expf(x); }
 // v_rcp_f32 (1 ulp).  `__frcp_rn` compiles to the IEEE-correct division sequence (v_div_scale x2, v_rcp, 4 FMAs, v_div_fmas,

@@ -2,14 +2,18 @@
 
 Import surface of the reference package (R/transvae/__init__.py:5-9): `from transvae import
 TransVAE, create_transvae, TransVAELoss`.  The loss re-exported here holds the closed-form L1 + KL terms
-(one fused HIP pass, transvae/losses/vae_loss.py); the reference's LPIPS / VF / GAN terms need external networks
-(`lpips` + VGG weights, DINOv2, a discriminator) and are out of scope.  The evaluation side (R/evaluate.py) is
-`evaluate` with per-image PSNR / SSIM / MSE from `reconstruction_metrics` (transvae/metrics.py), computed on the device.
+(one fused HIP pass, transvae/losses/vae_loss.py) and, given a `PerceptualLoss`, the reference's LPIPS term:
+`PerceptualLoss` (transvae/losses/lpips.py) is LPIPS-VGG on the HIP path -- thirteen ReLU convolutions through the same
+implicit-GEMM kernels as the model, max-pools and the LPIPS head in csrc/lpips.hip.  It ships WITHOUT weights: load the state
+dict of `lpips.LPIPS(net='vgg')` with `PerceptualLoss.from_file`.  The VF / GAN terms need other external
+networks (DINOv2, a discriminator) and are out of scope.  The evaluation side (R/evaluate.py) is `evaluate` with per-image
+PSNR / SSIM / MSE from `reconstruction_metrics` (transvae/metrics.py) and LPIPS from a `PerceptualLoss`, computed on the device.
 """
 from .evaluate import evaluate
+from .losses.lpips import PerceptualLoss
 from .losses.vae_loss import TransVAELoss
 from .metrics import reconstruction_metrics
 from .models.transvae import TransVAE, create_transvae
 
 __version__ = "0.2.0"
-__all__ = ["TransVAE", "create_transvae", "TransVAELoss", "reconstruction_metrics", "evaluate"]
+__all__ = ["TransVAE", "create_transvae", "TransVAELoss", "reconstruction_metrics", "evaluate", "PerceptualLoss"]

@@ -2,11 +2,13 @@
 
 The reference copies every batch to the host and runs skimage one image at a time; here the per-image values come from
 :func:`transvae.metrics.reconstruction_metrics` on the device (the reference's definitions: inputs clipped to [0, 1],
-skimage's 7x7 SSIM, data_range 1), stay there while the loop runs and reach the host once, at the end.
+skimage's 7x7 SSIM, data_range 1), stay there while the loop runs and reach the host once, at the end.  LPIPS follows
+R/evaluate.py:126-133: `lpips(images * 2 - 1, reconstruction * 2 - 1)` on the UNCLIPPED tensors, original first, from the
+`PerceptualLoss` handed in as `lpips_net`.
 """
 from __future__ import annotations
 
-from typing import Dict, Iterable, Sequence
+from typing import Dict, Iterable, Optional, Sequence
 
 import numpy as np
 import torch
@@ -17,22 +19,23 @@ _KNOWN = ("psnr", "ssim", "mse")
 
 
 def evaluate(model: torch.nn.Module, dataloader: Iterable, metrics: Sequence[str] = ("psnr", "ssim"),
-             device="cuda", per_image: bool = False) -> Dict[str, Dict]:
+             device="cuda", per_image: bool = False, lpips_net: Optional[torch.nn.Module] = None) -> Dict[str, Dict]:
     """{metric: {"mean", "std", "median"}} over every image of `dataloader`, like R/evaluate.py.
 
     `dataloader` yields `(images, labels)` pairs as in the reference (a bare image tensor is accepted too).  The model runs
     in eval mode under no_grad as `model(images)`, so z is sampled as in the reference.  Metrics: "psnr", "ssim" and "mse"
     (P/evaluate_transvae.py:134).  The statistics are NumPy's over the per-image values taken as float64 (`np.std` is the
-    population standard deviation).  "lpips" needs the external VGG network and raises ValueError.  per_image=True (not in
-    the reference) adds each metric's per-image values, in loader order, as a float64 array under "values".
+    population standard deviation).  "lpips" needs `lpips_net`, a `transvae.PerceptualLoss` with loaded weights on `device`
+    (the package ships none); without one it raises ValueError.  per_image=True (not in the reference) adds each metric's
+    per-image values, in loader order, as a float64 array under "values".
     """
     metrics = tuple(metrics)
-    if "lpips" in metrics:
-        raise ValueError("evaluate (HIP path): the LPIPS term needs the external VGG network (lpips package) and is outside "
-                         "this build; drop 'lpips' from metrics and compute it with the reference's own module")
-    unknown = [m for m in metrics if m not in _KNOWN]
+    if "lpips" in metrics and lpips_net is None:
+        raise ValueError("evaluate (HIP path): the LPIPS term needs the external VGG network's weights, which this package neither "
+                         "ships nor fetches; pass lpips_net=PerceptualLoss.from_file(...) or drop 'lpips' from metrics")
+    unknown = [m for m in metrics if m not in _KNOWN and m != "lpips"]
     if unknown or not metrics:
-        raise ValueError(f"evaluate: unknown metrics {unknown} (expected a non-empty subset of {list(_KNOWN)})")
+        raise ValueError(f"evaluate: unknown metrics {unknown} (expected a non-empty subset of {list(_KNOWN) + ['lpips']})")
     model.eval()
     values = {m: [] for m in metrics}
     with torch.no_grad():
@@ -40,7 +43,11 @@ def evaluate(model: torch.nn.Module, dataloader: Iterable, metrics: Sequence[str
             images = batch[0] if isinstance(batch, (tuple, list)) else batch
             images = images.to(device)
             reconstruction = model(images)[0]
-            batch_values = reconstruction_metrics(reconstruction, images, ssim_window="skimage", transform="clip", data_range=1.0)
+            batch_values = {}
+            if any(m in _KNOWN for m in metrics):
+                batch_values = reconstruction_metrics(reconstruction, images, ssim_window="skimage", transform="clip", data_range=1.0)
+            if "lpips" in metrics:
+                batch_values["lpips"] = lpips_net(images, reconstruction, normalize=True).reshape(-1)
             for m in metrics:
                 values[m].append(batch_values[m])
     results = {}

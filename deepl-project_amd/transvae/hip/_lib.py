@@ -20,6 +20,8 @@ SO_PATH = os.environ.get("TV_HIP_SO") or os.path.join(_HERE, "libtransvae_hip.so
 ACT_NONE, ACT_GELU, ACT_SILU = 0, 1, 2
 ACT_DERIV, ACT_SAVE_DERIV = 3, 16   # include/transvae_hip.h: saved tensor = act'(pre-activation)
 ACT_ADD = 4                         # aux_act of tv_igemm_nt_actgrad: out = conv + residual + aux (a second residual)
+ACTX_RELU = 5                       # TV_ACTX_RELU: desc.act of a ReLU layer; as aux_act / tv_act_bwd act the saved tensor is the layer's output
+LPIPS_MAP, LPIPS_SIGMOID, LPIPS_CLAMP = 1, 2, 4   # tv_lpips_prep flags
 SSIM_SKIMAGE, SSIM_BOX11 = 0, 1                 # tv_recon_metrics window kinds
 METRIC_NONE, METRIC_CLIP, METRIC_SIGMOID = 0, 1, 2   # tv_recon_metrics input transforms
 DERIVE_UP_FWD, DERIVE_UP_DGRAD, DERIVE_UP_WGRAD_FOLD, DERIVE_S2_PARITY = 1, 2, 3, 4   # tv_conv3x3_derived forms
@@ -80,6 +82,12 @@ SIGNATURES = {
     "tv_pack_weight_multi": (_I, [_P, _I, _LL, _P]),
     "tv_recon_metrics_partial_count": (_LL, [_I, _I, _I, _I, _I]),
     "tv_recon_metrics": (_I, [_P, _P] + [_LL] * 8 + [_I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "tv_maxpool2x2_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "tv_maxpool2x2_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "tv_lpips_prep": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "tv_lpips_prep_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "tv_lpips_head_partial_count": (_LL, [_I, _I, _I]),
+    "tv_lpips_head": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P]),
 }
 
 _lib = None

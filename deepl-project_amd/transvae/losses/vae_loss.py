@@ -2,9 +2,10 @@
 
 Interface mirror of R/transvae/losses/vae_loss.py (`TransVAELoss(l1_weight, lpips_weight, kl_weight, vf_weight, gan_weight,
 use_gan)`, `forward(reconstruction, target, mu, logvar, discriminator=None, dinov2=None) -> dict` with keys 'l1', 'kl', 'total').
-What is NOT here, and why: LPIPS (an external VGG network fetched over the network), VF (DINOv2) and the GAN term (a
-discriminator network) consume the path's outputs but are other networks -- out of scope; asking for them
-raises.  The two closed-form terms are
+The LPIPS term (vae_loss.py:86-91) is computed by a `PerceptualLoss` (transvae/losses/lpips.py, VGG-16 on the HIP path) handed in
+as `lpips_net`; its pretrained weights are not part of this package and cannot be fetched by it, so a non-zero lpips_weight
+WITHOUT an lpips_net raises.  VF (DINOv2) and the GAN term (a discriminator network) are other networks -- out of scope
+(SURVEY 2.1); asking for them raises.  The two closed-form terms are
 
     l1 = l1_weight * mean |reconstruction - target|                                   (vae_loss.py:83-84)
     kl = kl_weight * -0.5 * sum(1 + logvar - mu^2 - exp(logvar)) / (B * H_lat * W_lat)  (vae_loss.py:94-96)
@@ -74,19 +75,22 @@ def fused_l1_kl(reconstruction: torch.Tensor, target: torch.Tensor, mu: torch.Te
 class TransVAELoss(nn.Module):
     def __init__(self, l1_weight: float = 1.0, lpips_weight: float = 1.0, kl_weight: float = 1e-8, vf_weight: float = 0.1,
                  gan_weight: float = 0.05, use_gan: bool = False, sigmoid_recon: bool = False, kl_mean: bool = False,
-                 logvar_clip: Optional[Tuple[float, float]] = None):
+                 logvar_clip: Optional[Tuple[float, float]] = None, lpips_net: Optional[nn.Module] = None):
         """Defaults are the reference's (R/transvae/losses/vae_loss.py:31-38: lpips 1.0, vf 0.1, gan 0.05, use_gan False), so
-        `TransVAELoss()` cannot silently mean something else here: the LPIPS term (always on in the reference, VGG weights
-        from the network) is outside this build and a non-zero lpips_weight RAISES -- pass lpips_weight=0 for the closed-form
-        terms.  The VF and GAN terms only exist in the reference when its forward() is handed a DINOv2 model / a discriminator
-        (vae_loss.py:99-112); handing one to this forward() raises as well."""
+        `TransVAELoss()` cannot silently mean something else here: the LPIPS term (always on in the reference, which fetches
+        the VGG weights from the network) needs `lpips_net`, a `transvae.PerceptualLoss` with loaded weights; a non-zero
+        lpips_weight without one RAISES -- pass lpips_weight=0 for the closed-form terms alone.  The VF and GAN terms only
+        exist in the reference when its forward() is handed a DINOv2 model / a discriminator (vae_loss.py:99-112); handing
+        one to this forward() raises as well."""
         super().__init__()
-        if lpips_weight != 0.0:
-            raise ValueError("TransVAELoss (HIP path): the LPIPS term needs the external VGG network (lpips package) and is outside "
-                             "this build; construct with lpips_weight=0 (closed-form L1 + KL) and add LPIPS with the reference's own module")
+        if lpips_weight != 0.0 and lpips_net is None:
+            raise ValueError("TransVAELoss (HIP path): the LPIPS term needs the external VGG network's weights, which this package "
+                             "neither ships nor fetches; pass lpips_net=PerceptualLoss.from_file(...), or construct with "
+                             "lpips_weight=0 for the closed-form L1 + KL terms")
         self.l1_weight, self.lpips_weight, self.kl_weight = l1_weight, lpips_weight, kl_weight
         self.vf_weight, self.gan_weight, self.use_gan = vf_weight, gan_weight, use_gan
         self.sigmoid_recon, self.kl_mean, self.logvar_clip = sigmoid_recon, kl_mean, logvar_clip
+        self.lpips_net = lpips_net if lpips_weight != 0.0 else None   # a submodule: moves with .to(); buffers only, no parameters
 
     def forward(self, reconstruction, target, mu, logvar, discriminator=None, dinov2=None) -> dict:
         if (dinov2 is not None and self.vf_weight > 0) or (self.use_gan and discriminator is not None):
@@ -94,4 +98,10 @@ class TransVAELoss(nn.Module):
                              "without dinov2 / discriminator and add those terms with the reference's own modules")
         out = fused_l1_kl(reconstruction, target, mu, logvar, self.l1_weight, self.kl_weight, self.kl_mean, self.sigmoid_recon,
                           self.logvar_clip)
-        return {"l1": out[0], "kl": out[1], "total": out[2]}
+        if self.lpips_net is None:
+            return {"l1": out[0], "kl": out[1], "total": out[2]}
+        # lpips_weight * lpips(recon * 2 - 1, target * 2 - 1).mean() (vae_loss.py:86-91); under sigmoid_recon the patched copy's
+        # order: sigmoid, 2x - 1, clamp to [-1, 1] on both images (P/.../vae_loss.py:80-91) -- all inside the network's input pass
+        d = self.lpips_net.distance(reconstruction, target, normalize=True, sigmoid_input=self.sigmoid_recon, clamp=self.sigmoid_recon)
+        lp = d.mean() * self.lpips_weight
+        return {"l1": out[0], "lpips": lp, "kl": out[1], "total": out[0] + lp + out[1]}   # (the reference's sum order)

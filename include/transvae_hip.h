@@ -45,6 +45,11 @@ extern "C" {
  * R/transvae/modules/conv.py:85-104) */
 #define TV_ACT_ADD 4
 #define TV_ACT_SAVE_DERIV 16
+/* ReLU, for the frozen VGG layers of the perceptual loss (tv_igemm_nt desc.act; aux_act of tv_igemm_nt_actgrad and act of
+ * tv_act_bwd, where the "saved tensor" is the ReLU layer's own bf16 OUTPUT y and the factor is (y > 0) -- nothing else is
+ * saved for such a layer, and pre_act must be NULL).  The name is deliberately outside the TV_ACT_ family, whose six ids
+ * are pinned; csrc/common.h repeats it under the same name. */
+#define TV_ACTX_RELU 5
 
 /* library ------------------------------------------------------------------ */
 int tv_init(void);                 /* allocates the device zero page; idempotent */
@@ -317,6 +322,45 @@ int tv_recon_metrics(const float* recon, const float* target,
                      long long target_sn, long long target_sc, long long target_sh, long long target_sw,
                      int B, int C, int H, int W, int kind, int transform, float data_range,
                      float* partials, float* out, void* stream);
+
+/* LPIPS (VGG-16) perceptual term: everything that is not a convolution (csrc/lpips.hip) ---------------------------------------
+ * The network is lpips.LPIPS(net='vgg') as R/transvae/losses/vae_loss.py:52,88-91 and R/evaluate.py:87-90,126-133 use it:
+ * scaling layer, 13 3x3 convolutions + ReLU (tv_igemm_nt with TV_ACTX_RELU), four 2x2 max-pools, and on each of the five
+ * taps relu{1_2,2_2,3_3,4_3,5_3} the head below.  Activations bf16 NHWC, sums fp32.
+ *
+ * 2x2 / stride-2 max-pool with floor semantics (F.max_pool2d(x, 2)): x [B, H, W, C] -> y [B, H/2, W/2, C], C % 8 == 0.
+ * Backward recomputes the argmax from the saved input x (no index tensor) and routes gy to the FIRST maximum in torch's scan
+ * order (rows, then columns; a later element wins only if greater or NaN), so it equals torch's backward bit for bit on ties:
+ *     gx = route(gy) [+ add] [where x > 0, else 0]
+ * add (or NULL): a second gradient of the same tensor, joined in one fp32 sum with one rounding; relu_mask != 0: x is a ReLU
+ * output and gx is the gradient w.r.t. its pre-activation. */
+int tv_maxpool2x2_fwd(const void* x, void* y, int B, int H, int W, int C, void* stream);
+int tv_maxpool2x2_bwd(const void* x, const void* gy, const void* add, void* gx, int B, int H, int W, int C, int relu_mask,
+                      void* stream);
+/* Input preparation: fp32 NCHW images [B, 3, H, W] -> cols [Ba + Bb, H, W, 32] bf16, the 3x3 / pad-1 patches ((ky, kx, c)
+ * order, 27 of 32 used) of the scaled image, i.e. the operand of conv1_1 as a K = 32 GEMM.  Images 0 .. Ba-1 come from a with
+ * flags_a, the other Bb from b with flags_b (b may be NULL when Bb == 0).  Per element, in this order:
+ *   TV_LPIPS_SIGMOID  v = sigmoid(v)            (P/transvae/losses/vae_loss.py:80)
+ *   TV_LPIPS_MAP      v = 2 v - 1               ([0, 1] -> [-1, 1]: normalize=True of lpips, vae_loss.py:88-89)
+ *   TV_LPIPS_CLAMP    v = clamp(v, -1, 1)       (P/.../vae_loss.py:88-89)
+ * then LPIPS's scaling layer (v - shift[c]) / scale[c]; shift_scale = {shift[3], scale[3]} fp32 on the device.
+ * tv_lpips_prep_bwd is the adjoint for one source: dcols [B, H, W, 32] bf16 -> da [B, 3, H, W] fp32, the gradient w.r.t. a. */
+#define TV_LPIPS_MAP 1
+#define TV_LPIPS_SIGMOID 2
+#define TV_LPIPS_CLAMP 4
+int tv_lpips_prep(const float* a, const float* b, void* cols, int Ba, int Bb, int H, int W, int flags_a, int flags_b,
+                  const float* shift_scale, void* stream);
+int tv_lpips_prep_bwd(const void* dcols, const float* a, float* da, int B, int H, int W, int flags, const float* shift_scale,
+                      void* stream);
+/* Head of one tap.  feat [2B, HW, C] bf16: images 0 .. B-1 are x (reconstruction), B .. 2B-1 are t (target); w [C] fp32.
+ *     f = x / (sqrt(sum_c x_c^2) + 1e-10), g likewise from t, d = sum_c w_c (f_c - g_c)^2, out[b] = mean over pixels of d
+ * (accumulate != 0: out[b] += ..., the taps summed in call order).  grad (or NULL) [B, HW, C] bf16 receives
+ * upstream / HW * dd/dx in the same launch; a pixel whose x is all zero gets a zero gradient.  C a power of two in [8, 512].
+ * partials: tv_lpips_head_partial_count(B, HW, C) floats of scratch (-1: bad arguments); an image's partials are added in a
+ * fixed order by a finalise launch, so out[b] is bit-reproducible and independent of the rest of the batch. */
+long long tv_lpips_head_partial_count(int B, int HW, int C);
+int tv_lpips_head(const void* feat, const float* w, float* partials, float* out, void* grad, int B, int HW, int C,
+                  float upstream, int accumulate, void* stream);
 
 #ifdef __cplusplus
 }
