@@ -71,6 +71,12 @@ struct TvPerDeviceOnce {
 #ifndef TV_ACTX_RELU
 #define TV_ACTX_RELU 5
 #endif
+// LeakyReLU, slope 0.2 (the PatchGAN discriminator, csrc/gan.hip): same rules as TV_ACTX_RELU -- the saved tensor is the layer's
+// own bf16 OUTPUT y (slope > 0, so sign(y) = sign(z)) and the factor is y > 0 ? 1 : 0.2.
+#ifndef TV_ACTX_LRELU
+#define TV_ACTX_LRELU 6
+#endif
+#define TV_LRELU_SLOPE 0.2f
 
 __device__ __forceinline__ float tv_fast_exp(float x) { return __expf(x); }
 // v_rcp_f32 (1 ulp).  `__frcp_rn` compiles to the IEEE-correct division sequence (v_div_scale x2, v_rcp, 4 FMAs, v_div_fmas,

@@ -77,6 +77,9 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const bf16* __restrict__ z
         if (act == TV_ACTX_RELU) {   // z is the ReLU layer's OUTPUT; a select, so the kept gradients pass through bit for bit
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = (float)zv[e] > 0.f ? gv[e] : (bf16)0.f;
+        } else if (act == TV_ACTX_LRELU) {   // likewise the layer's OUTPUT: kept gradients exact, the others times the slope
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = (float)zv[e] > 0.f ? gv[e] : (bf16)((float)gv[e] * TV_LRELU_SLOPE);
         } else {
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = (bf16)((float)gv[e] * tv_act_grad_rt(act, (float)zv[e]));
@@ -327,7 +330,7 @@ extern "C" int tv_rope_qk(void* qkv, const float* tab, int B, int N, int heads, 
 
 extern "C" int tv_act_bwd(const void* z, const void* dy, void* dz, long long n, int act, void* stream) {
     TV_CHECK_ARG(z && dy && dz && n > 0 && n % 8 == 0, "tv_act_bwd: n=%lld must be a positive multiple of 8", n);
-    TV_CHECK_ARG((act >= 0 && act <= 2) || act == TV_ACTX_RELU, "tv_act_bwd: unknown activation %d", act);
+    TV_CHECK_ARG((act >= 0 && act <= 2) || act == TV_ACTX_RELU || act == TV_ACTX_LRELU, "tv_act_bwd: unknown activation %d", act);
     hipLaunchKernelGGL(act_bwd_kernel, dim3(ew_grid(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16*)z, (const bf16*)dy, (bf16*)dz,
                        n / 8, act);
     TV_CHECK_LAUNCH("tv_act_bwd");

@@ -237,7 +237,9 @@ enum { EF_GENERIC = 0, EF_PLAIN = 1, EF_GELU_D = 2, EF_SILU_D = 3, EF_GELU = 4, 
        EF_PLAIN_S1 = 10, EF_RES_S1 = 11, EF_DERIV_S1 = 12, EF_SILU_D_S2 = 13, EF_PLAIN_S2 = 14,
        EF_RES2 = 15,       // acc + residual + second residual (TV_ACT_ADD): two branch values join the stream in one fp32 sum
        EF_RELU = 16,       // max(acc + bias, 0): the frozen VGG layers of the perceptual loss (TV_ACTX_RELU)
-       EF_RELU_MASK = 17 };// acc where the layer's own bf16 OUTPUT (aux) is > 0, else 0: the data gradient through a ReLU layer
+       EF_RELU_MASK = 17,  // acc where the layer's own bf16 OUTPUT (aux) is > 0, else 0: the data gradient through a ReLU layer
+       EF_LRELU = 18,      // leaky ReLU (slope 0.2) of acc + bias: the first layer of the PatchGAN discriminator (TV_ACTX_LRELU)
+       EF_LRELU_MASK = 19 };// acc where the layer's own OUTPUT (aux) is > 0, else 0.2 acc: the data gradient through such a layer
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void epi_pair_exchange(bf16x8& a, bf16x8& b) {   // an involution: lanes fi < 8 keep a, lanes fi >= 8 keep b
@@ -329,6 +331,12 @@ __device__ __forceinline__ bf16x8 epi_math(float (&v)[8], const bf16x8& ld, cons
     } else if constexpr (FORM == EF_RELU_MASK) {   // (a select, not a multiply: the mask passes the value through exactly)
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = (float)ld[e] > 0.f ? v[e] : 0.f;
+    } else if constexpr (FORM == EF_LRELU) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * TV_LRELU_SLOPE;
+    } else if constexpr (FORM == EF_LRELU_MASK) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = (float)ld[e] > 0.f ? v[e] : v[e] * TV_LRELU_SLOPE;
     } else if constexpr (FORM == EF_GELU_D || FORM == EF_SILU_D) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -393,14 +401,15 @@ __device__ __forceinline__ void epilogue_direct(const IgemmArgs& p, const f32x4 
                                                 int lane, int nw0, RowMap m_of_row) {
     constexpr int MF = WTM / 16, NF = WTN / 16, NC = NF / 2;
     static_assert(NF % 2 == 0, "a lane's channels must come in whole 8-channel chunks");
-    constexpr bool LOADS = FORM == EF_RES || FORM == EF_DERIV || FORM == EF_RES_DERIV || FORM == EF_RES2 || FORM == EF_RELU_MASK;
+    constexpr bool LOADS = FORM == EF_RES || FORM == EF_DERIV || FORM == EF_RES_DERIV || FORM == EF_RES2 || FORM == EF_RELU_MASK ||
+                           FORM == EF_LRELU_MASK;
     constexpr bool LOADS2 = FORM == EF_RES_DERIV || FORM == EF_RES2;
     constexpr bool SAVES = FORM == EF_GELU_D || FORM == EF_SILU_D;
     // fragment rows per batch: the loads of a whole batch are issued before its arithmetic (their latency runs once per
     // batch, not once per line; one load per line in flight measured 0.96-0.99x of the LDS form, which batches them)
     constexpr int IB = !LOADS ? 1 : (MF % 4 == 0 && !LOADS2 ? 4 : (MF % 2 == 0 ? 2 : 1));
     const int fq = lane >> 4, fi = lane & 15;
-    const bf16* __restrict__ lsrc = (FORM == EF_DERIV || FORM == EF_RELU_MASK) ? p.aux : p.res;
+    const bf16* __restrict__ lsrc = (FORM == EF_DERIV || FORM == EF_RELU_MASK || FORM == EF_LRELU_MASK) ? p.aux : p.res;
     const bf16* __restrict__ lsrc2 = p.aux;
     const int lidx = epi_line_index(lane), hidx = epi_half_index(lane);
     const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -755,6 +764,9 @@ __device__ __forceinline__ void epilogue_lds(const IgemmArgs& p, const f32x4 (&a
                 } else if (p.aux_act == TV_ACTX_RELU) {   // aux is the ReLU layer's own output: its sign is the mask
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = (float)av[e] > 0.f ? v[e] : 0.f;
+                } else if (p.aux_act == TV_ACTX_LRELU) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[e] = (float)av[e] > 0.f ? v[e] : v[e] * TV_LRELU_SLOPE;
                 } else {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] *= tv_act_grad_rt(p.aux_act, (float)av[e]);
@@ -763,6 +775,9 @@ __device__ __forceinline__ void epilogue_lds(const IgemmArgs& p, const f32x4 (&a
                 if (p.act == TV_ACTX_RELU) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
+                } else if (p.act == TV_ACTX_LRELU) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * TV_LRELU_SLOPE;
                 } else if (!save_deriv) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = tv_act_rt(p.act, v[e]);
@@ -808,6 +823,8 @@ __device__ __forceinline__ void epilogue(const IgemmArgs& p, const f32x4 (&acc)[
                 case EF_RES2: epilogue_direct<WTM, WTN, EF_RES2>(p, acc, bv, lane, nw0, m_of_row); return;
                 case EF_RELU: epilogue_direct<WTM, WTN, EF_RELU>(p, acc, bv, lane, nw0, m_of_row); return;
                 case EF_RELU_MASK: epilogue_direct<WTM, WTN, EF_RELU_MASK>(p, acc, bv, lane, nw0, m_of_row); return;
+                case EF_LRELU: epilogue_direct<WTM, WTN, EF_LRELU>(p, acc, bv, lane, nw0, m_of_row); return;
+                case EF_LRELU_MASK: epilogue_direct<WTM, WTN, EF_LRELU_MASK>(p, acc, bv, lane, nw0, m_of_row); return;
                 case EF_ROPE: epilogue_direct<WTM, WTN, EF_ROPE>(p, acc, bv, lane, nw0, m_of_row); return;
                 case EF_PLAIN_S1: epilogue_direct<WTM, WTN, EF_PLAIN, 1>(p, acc, bv, lane, nw0, m_of_row); return;
                 case EF_RES_S1: epilogue_direct<WTM, WTN, EF_RES, 1>(p, acc, bv, lane, nw0, m_of_row); return;

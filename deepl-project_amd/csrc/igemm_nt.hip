@@ -954,6 +954,7 @@ int epilogue_form(const IgemmArgs& a) {
     if (a.rope) return (!a.aux && !a.res && !a.pre && a.act == TV_ACT_NONE && a.rope_cols % 32 == 0) ? EF_ROPE : EF_GENERIC;
     if (a.aux) {
         if (a.aux_act == TV_ACTX_RELU) return (!a.res && !a.pre && a.act == TV_ACT_NONE) ? EF_RELU_MASK : EF_GENERIC;
+        if (a.aux_act == TV_ACTX_LRELU) return (!a.res && !a.pre && a.act == TV_ACT_NONE) ? EF_LRELU_MASK : EF_GENERIC;
         if (!a.res || a.pre || a.act != TV_ACT_NONE) return EF_GENERIC;
         return a.aux_act == TV_ACT_DERIV ? EF_RES_DERIV : (a.aux_act == TV_ACT_ADD ? EF_RES2 : EF_GENERIC);
     }
@@ -963,6 +964,7 @@ int epilogue_form(const IgemmArgs& a) {
         return a.act == TV_ACT_GELU ? EF_GELU_D : (a.act == TV_ACT_SILU ? EF_SILU_D : EF_GENERIC);
     }
     if (a.act == TV_ACTX_RELU) return EF_RELU;
+    if (a.act == TV_ACTX_LRELU) return EF_LRELU;
     return a.act == TV_ACT_NONE ? EF_PLAIN : (a.act == TV_ACT_GELU ? EF_GELU : (a.act == TV_ACT_SILU ? EF_SILU : EF_GENERIC));
 }
 
@@ -1215,7 +1217,7 @@ extern "C" int tv_igemm_nt(const tv_conv_desc* d, const void* x, const void* w, 
 
 extern "C" int tv_igemm_nt_actgrad(const tv_conv_desc* d, const void* x, const void* w, const void* residual,
                                    const void* aux_pre_act, int aux_act, void* out, void* stream) {
-    TV_CHECK_ARG(aux_pre_act && aux_act >= 0 && aux_act <= TV_ACTX_RELU && d && d->act == TV_ACT_NONE,
+    TV_CHECK_ARG(aux_pre_act && aux_act >= 0 && aux_act <= TV_ACTX_LRELU && d && d->act == TV_ACT_NONE,
                  "tv_igemm_nt_actgrad: needs the saved pre-activation, a valid activation id and desc.act == NONE");
     return igemm_nt_impl(d, x, w, nullptr, residual, nullptr, out, aux_pre_act, aux_act, stream);
 }
@@ -1243,10 +1245,10 @@ static int igemm_nt_impl(const tv_conv_desc* d, const void* x, const void* w, co
     TV_CHECK_ARG(d->batch > 0 && d->h_in > 0 && d->w_in > 0 && d->h_out > 0 && d->w_out > 0, "tv_igemm_nt: empty geometry");
     TV_CHECK_ARG(d->kh > 0 && d->kw > 0 && d->stride > 0 && d->pad >= 0, "tv_igemm_nt: bad taps");
     TV_CHECK_ARG((d->up_shift | 1) == 1 && (d->dil_mask | 1) == 1, "tv_igemm_nt: up_shift/dil_mask must be 0 or 1");
-    TV_CHECK_ARG(d->act >= 0 && ((d->act & ~TV_ACT_SAVE_DERIV) <= 2 || d->act == TV_ACTX_RELU), "tv_igemm_nt: unknown activation %d", d->act);
+    TV_CHECK_ARG(d->act >= 0 && ((d->act & ~TV_ACT_SAVE_DERIV) <= 2 || d->act == TV_ACTX_RELU || d->act == TV_ACTX_LRELU), "tv_igemm_nt: unknown activation %d", d->act);
     TV_CHECK_ARG(!(d->act & TV_ACT_SAVE_DERIV) || (pre_act && (d->act & ~TV_ACT_SAVE_DERIV) != TV_ACT_NONE),
                  "tv_igemm_nt: TV_ACT_SAVE_DERIV needs an activation and a pre_act buffer");
-    TV_CHECK_ARG(d->act != TV_ACTX_RELU || !pre_act, "tv_igemm_nt: a ReLU layer saves nothing (its output is its own backward mask): pre_act must be NULL");
+    TV_CHECK_ARG((d->act != TV_ACTX_RELU && d->act != TV_ACTX_LRELU) || !pre_act, "tv_igemm_nt: a ReLU / LeakyReLU layer saves nothing (its output is its own backward mask): pre_act must be NULL");
     TV_CHECK_ARG(d->store_shuffle >= 0 && d->store_shuffle <= 2, "tv_igemm_nt: store_shuffle must be 0, 1 or 2");
     const long long M = (long long)d->batch * d->h_out * d->w_out;
     TV_CHECK_ARG(M < (1ll << 31) && (long long)d->batch * d->h_in * d->w_in < (1ll << 31), "tv_igemm_nt: too many pixels");

@@ -5,15 +5,19 @@ TransVAE, create_transvae, TransVAELoss`.  The loss re-exported here holds the c
 (one fused HIP pass, transvae/losses/vae_loss.py) and, given a `PerceptualLoss`, the reference's LPIPS term:
 `PerceptualLoss` (transvae/losses/lpips.py) is LPIPS-VGG on the HIP path -- thirteen ReLU convolutions through the same
 implicit-GEMM kernels as the model, max-pools and the LPIPS head in csrc/lpips.hip.  It ships WITHOUT weights: load the state
-dict of `lpips.LPIPS(net='vgg')` with `PerceptualLoss.from_file`.  The VF / GAN terms need other external
-networks (DINOv2, a discriminator) and are out of scope.  The evaluation side (R/evaluate.py) is `evaluate` with per-image
+dict of `lpips.LPIPS(net='vgg')` with `PerceptualLoss.from_file`.  The adversarial stage (stage 2 of the
+reference's configs) is `TransVAELoss(use_gan=True)` handed a discriminator, `DiscriminatorLoss` for the discriminator's own
+objective, and `PatchDiscriminator` (transvae/models/discriminator.py), the 70x70 PatchGAN on the HIP path, trained from
+scratch.  The VF term needs DINOv2's trained weights and is out of scope.  The evaluation side (R/evaluate.py) is `evaluate` with per-image
 PSNR / SSIM / MSE from `reconstruction_metrics` (transvae/metrics.py) and LPIPS from a `PerceptualLoss`, computed on the device.
 """
 from .evaluate import evaluate
 from .losses.lpips import PerceptualLoss
-from .losses.vae_loss import TransVAELoss
+from .losses.vae_loss import DiscriminatorLoss, TransVAELoss
 from .metrics import reconstruction_metrics
+from .models.discriminator import PatchDiscriminator
 from .models.transvae import TransVAE, create_transvae
 
 __version__ = "0.2.0"
-__all__ = ["TransVAE", "create_transvae", "TransVAELoss", "reconstruction_metrics", "evaluate", "PerceptualLoss"]
+__all__ = ["TransVAE", "create_transvae", "TransVAELoss", "reconstruction_metrics", "evaluate", "PerceptualLoss", "DiscriminatorLoss",
+           "PatchDiscriminator"]

@@ -21,6 +21,8 @@ ACT_NONE, ACT_GELU, ACT_SILU = 0, 1, 2
 ACT_DERIV, ACT_SAVE_DERIV = 3, 16   # include/transvae_hip.h: saved tensor = act'(pre-activation)
 ACT_ADD = 4                         # aux_act of tv_igemm_nt_actgrad: out = conv + residual + aux (a second residual)
 ACTX_RELU = 5                       # TV_ACTX_RELU: desc.act of a ReLU layer; as aux_act / tv_act_bwd act the saved tensor is the layer's output
+ACTX_LRELU = 6                      # TV_ACTX_LRELU: LeakyReLU(0.2), same rules as ACTX_RELU (the PatchGAN discriminator)
+GAN_GEN, GAN_BCE, GAN_HINGE, GAN_WGAN = 0, 1, 2, 3   # tv_gan_loss modes
 LPIPS_MAP, LPIPS_SIGMOID, LPIPS_CLAMP = 1, 2, 4   # tv_lpips_prep flags
 SSIM_SKIMAGE, SSIM_BOX11 = 0, 1                 # tv_recon_metrics window kinds
 METRIC_NONE, METRIC_CLIP, METRIC_SIGMOID = 0, 1, 2   # tv_recon_metrics input transforms
@@ -88,6 +90,15 @@ SIGNATURES = {
     "tv_lpips_prep_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "tv_lpips_head_partial_count": (_LL, [_I, _I, _I]),
     "tv_lpips_head": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P]),
+    "tv_patch4x4s2": (_I, [_P, _LL, _LL, _LL, _LL, _P, _I, _I, _I, _I, _P]),
+    "tv_patch4x4s2_bwd": (_I, [_P, _P, _LL, _LL, _LL, _LL, _P, _I, _I, _I, _I, _P]),
+    "tv_bn_partial_count": (_LL, [_LL, _I]),
+    "tv_bn_stats": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _F, _F, _P]),
+    "tv_bn_lrelu_apply": (_I, [_P, _P, _P, _LL, _I, _P]),
+    "tv_bn_lrelu_bwd_reduce": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _I, _P]),
+    "tv_bn_lrelu_bwd_apply": (_I, [_P, _P, _P, _P, _P, _P, _LL, _I, _I, _P]),
+    "tv_gan_loss_partial_count": (_LL, [_LL, _LL]),
+    "tv_gan_loss": (_I, [_P, _P, _P, _P, _P, _P, _LL, _LL, _I, _F, _P]),
 }
 
 _lib = None

@@ -416,6 +416,12 @@ class _Geo:
                 self.Ho, self.Wo = self.H // 2, self.W // 2
             elif mode == "c3up":
                 self.Ho, self.Wo = 2 * self.H, 2 * self.W
+            elif mode == "c4s2":   # 4x4 / stride 2 / pad 1 (PatchGAN discriminator)
+                _require(self.H % 2 == 0 and self.W % 2 == 0, "operand check failed: self.H % 2 == 0 and self.W % 2 == 0")
+                self.Ho, self.Wo = self.H // 2, self.W // 2
+            elif mode == "c4s1":   # 4x4 / stride 1 / pad 1: the grid shrinks by one (odd grids occur)
+                _require(self.H >= 2 and self.W >= 2, "operand check failed: self.H >= 2 and self.W >= 2")
+                self.Ho, self.Wo = self.H - 1, self.W - 1
             elif mode == "shuf":
                 _require(self.KH == 1 and self.KW == 1 and self.Cout % 4 == 0, "operand check failed: self.KH == 1 and self.KW == 1 and self.Cout % 4 == 0")
                 self.Ho, self.Wo = self.H, self.W          # GEMM grid; stored to [B,2H,2W,Cout/4]
@@ -426,7 +432,8 @@ class _Geo:
             else:
                 self.out_shape = (self.B, self.Ho, self.Wo, self.Cout)
         _require(w.shape[-1] == self.Cin, "operand check failed: " + repr((mode, tuple(x.shape), tuple(w.shape))))
-        exp_k = {"linear": (1, 1), "c3s1": (3, 3), "c3s2": (3, 3), "c3up": (3, 3), "unshuf": (2, 2), "shuf": (1, 1)}[mode]
+        exp_k = {"linear": (1, 1), "c3s1": (3, 3), "c3s2": (3, 3), "c3up": (3, 3), "unshuf": (2, 2), "shuf": (1, 1), "c4s2": (4, 4),
+                 "c4s1": (4, 4)}[mode]
         _require((self.KH, self.KW) == exp_k, "operand check failed: " + repr((mode, tuple(w.shape))))
 
     def fwd_desc(self, act: int) -> L.ConvDesc:
@@ -444,6 +451,10 @@ class _Geo:
             return _desc(**common, stride=1, pad=1, up_shift=1)
         if m == "unshuf":
             return _desc(**common, stride=2, pad=0)
+        if m == "c4s2":
+            return _desc(**common, stride=2, pad=1)
+        if m == "c4s1":
+            return _desc(**common, stride=1, pad=1)
         if m == "shuf":
             common["ldo"] = self.Cout // 4
             return _desc(**common, store_shuffle=1)
@@ -740,6 +751,23 @@ def flush_deferred_grads():
                 pb3.grad = db3 if pb3.grad is None else pb3.grad.add_(db3)
 
 
+# data-gradient form of the 4x4 / stride-2 convolutions ('c4s2'): "polyphase" (2x2 footprint, phase-shuffled store) or "dilated"
+# (4x4 taps over the zero-dilated gradient); tools/gan_bench.py times both
+C4S2_DGRAD_FORM = "polyphase"
+_C4S2_KY = ((3, 1), (2, 0))    # [phase][tap] -> ky
+
+
+def _c4s2_poly_weight(w: torch.Tensor, Cout: int, Cin: int) -> torch.Tensor:
+    """w fp32 [Cout, 4, 4, Cin] -> bf16 [4*Cin, 2, 2, Cout]: row (2*py+px)*Cin + ci, tap (ty, tx) = w[co, ky(py,ty), kx(px,tx), ci]."""
+    wt = w.permute(3, 1, 2, 0)                                   # [Cin, ky, kx, Cout]
+    out = torch.empty((4, Cin, 2, 2, Cout), dtype=BF16, device=w.device)
+    for py in range(2):
+        for px in range(2):
+            sel = wt[:, list(_C4S2_KY[py])][:, :, list(_C4S2_KY[px])]
+            out[2 * py + px] = sel.to(BF16)
+    return out.view(4 * Cin, 2, 2, Cout)
+
+
 def conv_dgrad(g: _Geo, w, gz, x_shape, residual=None, aux=None, aux_act: int = 0):
     """Gradient w.r.t. the layer input.  Optional fusions (one kernel, no extra pass):
     residual: a second gradient of the same tensor to add;  aux/aux_act: multiply by act'(aux), i.e. return the
@@ -750,10 +778,10 @@ def conv_dgrad(g: _Geo, w, gz, x_shape, residual=None, aux=None, aux_act: int = 
     dev = gz.device
     if m == "unshuf":  # GEMM rows n = (dy,dx,c): transpose the flattened [Cout, 4*Cin] matrix
         _, wt = pack_weight(w.view(g.Cout, 1, T * g.Cin), False, True, False)
-    elif m in ("c3s2", "c3up"):
+    elif m in ("c3s2", "c3up") or (m == "c4s2" and C4S2_DGRAD_FORM == "polyphase"):
         wt = None      # (parity / polyphase formulations below build their own operands)
-    else:              # [Cin][taps (reversed for 3x3)][Cout]
-        _, wt = pack_weight(w.view(g.Cout, T, g.Cin), False, True, m == "c3s1")
+    else:              # [Cin][taps (reversed for 3x3 / 4x4)][Cout]
+        _, wt = pack_weight(w.view(g.Cout, T, g.Cin), False, True, m in ("c3s1", "c4s1", "c4s2"))
     dx = torch.empty(x_shape, dtype=BF16, device=dev)
     if m == "linear":
         d = _desc(batch=g.B, h_in=1, w_in=1, c_in=g.Cout, ldx=g.Cout, h_out=1, w_out=1, c_out=g.Cin, ldo=g.Cin, kh=1, kw=1)
@@ -776,6 +804,23 @@ def conv_dgrad(g: _Geo, w, gz, x_shape, residual=None, aux=None, aux_act: int = 
         d = _desc(batch=g.B, h_in=g.Ho, w_in=g.Wo, c_in=g.Cout, ldx=g.Cout, h_out=g.H, w_out=g.W, c_out=g.Cin, ldo=g.Cin,
                   kh=4, kw=4, stride=2, pad=1)
         _igemm_bwd(d, gz, wd, residual, aux, aux_act, dx)
+    elif m == "c4s1":   # dx[iy] = sum_ky gz[iy + 1 - ky] w[ky]: taps reversed (t = 3 - ky), gz row iy + t - 2, i.e. pad 2
+        d = _desc(batch=g.B, h_in=g.Ho, w_in=g.Wo, c_in=g.Cout, ldx=g.Cout, h_out=g.H, w_out=g.W, c_out=g.Cin, ldo=g.Cin,
+                  kh=4, kw=4, stride=1, pad=2)
+        _igemm_bwd(d, gz, wt, residual, aux, aux_act, dx)
+    elif m == "c4s2" and C4S2_DGRAD_FORM == "polyphase":
+        # The adjoint of a 4x4 / stride-2 / pad-1 convolution is the polyphase upsampling convolution of 'c3up': dx row
+        # Y = 2y - py only sees ky of one parity, at gz rows y-1 (tap 0) and y (tap 1) of cell y on the (Ho+1)-cell grid:
+        #     py = 0: tap 0 <- ky 3, tap 1 <- ky 1        py = 1: tap 0 <- ky 2, tap 1 <- ky 0        (the same along x)
+        # 4 tap-GEMMs per output pixel instead of the 16 (12 of them on zeros) of the zero-dilated form.
+        wd = _derived_weight(w, "c4s2_poly", lambda: _c4s2_poly_weight(w, g.Cout, g.Cin))
+        d = _desc(batch=g.B, h_in=g.Ho, w_in=g.Wo, c_in=g.Cout, ldx=g.Cout, h_out=g.Ho + 1, w_out=g.Wo + 1, c_out=4 * g.Cin,
+                  ldo=g.Cin, kh=2, kw=2, stride=1, pad=1, store_shuffle=2)
+        _igemm_bwd(d, gz, wd, residual, aux, aux_act, dx)
+    elif m == "c4s2":   # zero-dilated form: virtual row uy = iy + t - 2 of the dilated gradient, valid where even, gz row uy / 2
+        d = _desc(batch=g.B, h_in=g.Ho, w_in=g.Wo, c_in=g.Cout, ldx=g.Cout, h_out=g.H, w_out=g.W, c_out=g.Cin, ldo=g.Cin,
+                  kh=4, kw=4, stride=1, pad=2, up_shift=1, dil_mask=1)
+        _igemm_bwd(d, gz, wt, residual, aux, aux_act, dx)
     elif m == "unshuf":
         # dx[b,2oy+dy,2ox+dx,c] = sum_co gz[b,oy,ox,co] W[co,dy,dx,c]  -> GEMM with shuffled store
         d = _desc(batch=g.B, h_in=g.Ho, w_in=g.Wo, c_in=g.Cout, ldx=g.Cout, h_out=g.Ho, w_out=g.Wo, c_out=4 * g.Cin, ldo=g.Cin,

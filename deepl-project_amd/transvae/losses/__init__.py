@@ -1,4 +1,4 @@
 from .lpips import PerceptualLoss
-from .vae_loss import TransVAELoss, fused_l1_kl
+from .vae_loss import DiscriminatorLoss, TransVAELoss, fused_l1_kl, generator_gan_loss
 
-__all__ = ["TransVAELoss", "fused_l1_kl", "PerceptualLoss"]
+__all__ = ["TransVAELoss", "fused_l1_kl", "PerceptualLoss", "DiscriminatorLoss", "generator_gan_loss"]

@@ -4,8 +4,10 @@ Interface mirror of R/transvae/losses/vae_loss.py (`TransVAELoss(l1_weight, lpip
 use_gan)`, `forward(reconstruction, target, mu, logvar, discriminator=None, dinov2=None) -> dict` with keys 'l1', 'kl', 'total').
 The LPIPS term (vae_loss.py:86-91) is computed by a `PerceptualLoss` (transvae/losses/lpips.py, VGG-16 on the HIP path) handed in
 as `lpips_net`; its pretrained weights are not part of this package and cannot be fetched by it, so a non-zero lpips_weight
-WITHOUT an lpips_net raises.  VF (DINOv2) and the GAN term (a discriminator network) are other networks -- out of scope
-(SURVEY 2.1); asking for them raises.  The two closed-form terms are
+WITHOUT an lpips_net raises.  VF (DINOv2) needs another network's trained weights -- out of scope; asking for it
+raises.  The GAN term (vae_loss.py:103-111) takes the caller's discriminator -- `transvae.PatchDiscriminator` on the HIP path,
+or any module returning logits -- and `DiscriminatorLoss` (vae_loss.py:199-244) is the discriminator's own objective; both
+run through `tv_gan_loss`, value and gradients in one pass.  The two closed-form terms are
 
     l1 = l1_weight * mean |reconstruction - target|                                   (vae_loss.py:83-84)
     kl = kl_weight * -0.5 * sum(1 + logvar - mu^2 - exp(logvar)) / (B * H_lat * W_lat)  (vae_loss.py:94-96)
@@ -72,6 +74,59 @@ def fused_l1_kl(reconstruction: torch.Tensor, target: torch.Tensor, mu: torch.Te
     return _FusedL1KL.apply(reconstruction, target, mu, logvar, l1_weight, kl_weight, kl_mean, sigmoid_recon, lo, hi)
 
 
+_GAN_MODES = {"bce": L.GAN_BCE, "hinge": L.GAN_HINGE, "wgan": L.GAN_WGAN}
+
+
+class _GanLossFn(torch.autograd.Function):
+    """tv_gan_loss: the weighted value of one GAN term and, in the same pass, its gradient(s) w.r.t. the logits."""
+
+    @staticmethod
+    def forward(ctx, a, b, mode, weight):
+        ops._need_gpu(a, b)
+        ops._require(a.dtype == torch.float32 and (b is None or b.dtype == torch.float32), "GAN loss: logits must be fp32")
+        ops._require(a.numel() > 0 and (b is None or b.numel() > 0), "GAN loss: empty logits")
+        a_c = a.contiguous()
+        b_c = b.contiguous() if b is not None else None
+        lib = L.load()
+        n_a, n_b = a_c.numel(), (b_c.numel() if b_c is not None else 0)
+        da = torch.empty_like(a_c) if ctx.needs_input_grad[0] else None
+        db = torch.empty_like(b_c) if (b_c is not None and ctx.needs_input_grad[1]) else None
+        part = torch.empty((lib.tv_gan_loss_partial_count(n_a, n_b),), dtype=torch.float32, device=a.device)
+        out = torch.empty((1,), dtype=torch.float32, device=a.device)
+        with torch.cuda.device(a.device):
+            L.check(lib.tv_gan_loss(ops._p(a_c), ops._p(b_c), ops._p(da), ops._p(db), ops._p(part), ops._p(out), n_a, n_b, int(mode),
+                                    float(weight), ops._stream()), "tv_gan_loss")
+        ctx.save_for_backward(da, db)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        da, db = ctx.saved_tensors
+        return (da * g if da is not None else None), (db * g if db is not None else None), None, None
+
+
+def generator_gan_loss(fake_pred: torch.Tensor, weight: float = 1.0) -> torch.Tensor:
+    """weight * binary_cross_entropy_with_logits(fake_pred, ones) (vae_loss.py:106-111), fp32 logits of any shape."""
+    return _GanLossFn.apply(fake_pred.float(), None, L.GAN_GEN, weight)
+
+
+class DiscriminatorLoss(nn.Module):
+    """R/transvae/losses/vae_loss.py:199-244: 'bce' and 'hinge' are (real + fake) / 2, 'wgan' is -mean(real) + mean(fake).
+    Value and both gradients come from one HIP pass over the two logit tensors (fp32, any shape)."""
+
+    def __init__(self, loss_type: str = "bce"):
+        super().__init__()
+        if loss_type not in _GAN_MODES:
+            raise ValueError(f"Unknown loss type: {loss_type}")
+        self.loss_type = loss_type
+
+    def forward(self, real_pred: torch.Tensor, fake_pred: torch.Tensor) -> torch.Tensor:
+        if self.loss_type not in _GAN_MODES:    # (the attribute is public, as in the reference, which checks here)
+            raise ValueError(f"Unknown loss type: {self.loss_type}")
+        with torch.autocast("cuda", enabled=False):
+            return _GanLossFn.apply(real_pred.float(), fake_pred.float(), _GAN_MODES[self.loss_type], 1.0)
+
+
 class TransVAELoss(nn.Module):
     def __init__(self, l1_weight: float = 1.0, lpips_weight: float = 1.0, kl_weight: float = 1e-8, vf_weight: float = 0.1,
                  gan_weight: float = 0.05, use_gan: bool = False, sigmoid_recon: bool = False, kl_mean: bool = False,
@@ -79,9 +134,10 @@ class TransVAELoss(nn.Module):
         """Defaults are the reference's (R/transvae/losses/vae_loss.py:31-38: lpips 1.0, vf 0.1, gan 0.05, use_gan False), so
         `TransVAELoss()` cannot silently mean something else here: the LPIPS term (always on in the reference, which fetches
         the VGG weights from the network) needs `lpips_net`, a `transvae.PerceptualLoss` with loaded weights; a non-zero
-        lpips_weight without one RAISES -- pass lpips_weight=0 for the closed-form terms alone.  The VF and GAN terms only
-        exist in the reference when its forward() is handed a DINOv2 model / a discriminator (vae_loss.py:99-112); handing
-        one to this forward() raises as well."""
+        lpips_weight without one RAISES -- pass lpips_weight=0 for the closed-form terms alone.  The VF term only exists in
+        the reference when its forward() is handed a DINOv2 model (vae_loss.py:99-101); handing one to this forward() raises.
+        The GAN term exists, as in the reference, when use_gan is set AND forward() is handed a discriminator
+        (vae_loss.py:103-111)."""
         super().__init__()
         if lpips_weight != 0.0 and lpips_net is None:
             raise ValueError("TransVAELoss (HIP path): the LPIPS term needs the external VGG network's weights, which this package "
@@ -93,15 +149,32 @@ class TransVAELoss(nn.Module):
         self.lpips_net = lpips_net if lpips_weight != 0.0 else None   # a submodule: moves with .to(); buffers only, no parameters
 
     def forward(self, reconstruction, target, mu, logvar, discriminator=None, dinov2=None) -> dict:
-        if (dinov2 is not None and self.vf_weight > 0) or (self.use_gan and discriminator is not None):
-            raise ValueError("TransVAELoss (HIP path): VF (DINOv2) and GAN (discriminator) terms are outside this build; call "
-                             "without dinov2 / discriminator and add those terms with the reference's own modules")
+        if dinov2 is not None and self.vf_weight > 0:
+            raise ValueError("TransVAELoss (HIP path): the VF (DINOv2) term is outside this build; call without dinov2 and add "
+                             "that term with the reference's own module")
         out = fused_l1_kl(reconstruction, target, mu, logvar, self.l1_weight, self.kl_weight, self.kl_mean, self.sigmoid_recon,
                           self.logvar_clip)
+        gan = None
+        if self.use_gan and discriminator is not None and (self.gan_weight > 0 or not self.sigmoid_recon):
+            # gan_weight * BCE_with_logits(D(reconstruction), ones) (vae_loss.py:103-111); the patched copy feeds the
+            # discriminator sigmoid(reconstruction) and only when gan_weight > 0 (P/.../vae_loss.py:114-115)
+            gan = self._gan_term(reconstruction, discriminator)
         if self.lpips_net is None:
-            return {"l1": out[0], "kl": out[1], "total": out[2]}
+            if gan is None:
+                return {"l1": out[0], "kl": out[1], "total": out[2]}
+            return {"l1": out[0], "kl": out[1], "gan": gan, "total": out[0] + out[1] + gan}
         # lpips_weight * lpips(recon * 2 - 1, target * 2 - 1).mean() (vae_loss.py:86-91); under sigmoid_recon the patched copy's
         # order: sigmoid, 2x - 1, clamp to [-1, 1] on both images (P/.../vae_loss.py:80-91) -- all inside the network's input pass
         d = self.lpips_net.distance(reconstruction, target, normalize=True, sigmoid_input=self.sigmoid_recon, clamp=self.sigmoid_recon)
         lp = d.mean() * self.lpips_weight
-        return {"l1": out[0], "lpips": lp, "kl": out[1], "total": out[0] + lp + out[1]}   # (the reference's sum order)
+        if gan is None:
+            return {"l1": out[0], "lpips": lp, "kl": out[1], "total": out[0] + lp + out[1]}   # (the reference's sum order)
+        return {"l1": out[0], "lpips": lp, "kl": out[1], "gan": gan, "total": out[0] + lp + out[1] + gan}
+
+    def _gan_term(self, reconstruction, discriminator):
+        if getattr(discriminator, "takes_sigmoid_flag", False):     # PatchDiscriminator: the sigmoid rides on its input pass
+            fake_pred = discriminator(reconstruction, sigmoid_input=self.sigmoid_recon)
+        else:
+            fake_pred = discriminator(torch.sigmoid(reconstruction) if self.sigmoid_recon else reconstruction)
+        with torch.autocast("cuda", enabled=False):
+            return generator_gan_loss(fake_pred, self.gan_weight)

@@ -50,6 +50,10 @@ extern "C" {
  * saved for such a layer, and pre_act must be NULL).  The name is deliberately outside the TV_ACT_ family, whose six ids
  * are pinned; csrc/common.h repeats it under the same name. */
 #define TV_ACTX_RELU 5
+/* LeakyReLU with the fixed slope 0.2 (the PatchGAN discriminator, csrc/gan.hip), under the same rules as TV_ACTX_RELU: as
+ * desc.act nothing is saved (pre_act NULL); as aux_act / tv_act_bwd act the "saved tensor" is the layer's own bf16 OUTPUT y
+ * (slope > 0, so sign(y) = sign(z)) and the factor is y > 0 ? 1 : 0.2. */
+#define TV_ACTX_LRELU 6
 
 /* library ------------------------------------------------------------------ */
 int tv_init(void);                 /* allocates the device zero page; idempotent */
@@ -361,6 +365,54 @@ int tv_lpips_prep_bwd(const void* dcols, const float* a, float* da, int B, int H
 long long tv_lpips_head_partial_count(int B, int HW, int C);
 int tv_lpips_head(const void* feat, const float* w, float* partials, float* out, void* grad, int B, int HW, int C,
                   float upstream, int accumulate, void* stream);
+
+/* The adversarial stage (csrc/gan.hip): a 70x70 PatchGAN discriminator and the GAN loss terms ----------------------------------
+ * R/transvae/losses/vae_loss.py:103-111 (generator term), :199-244 (DiscriminatorLoss).  The reference ships no discriminator
+ * network; the one built here is Conv(3,ndf,4,s2,p1)+LeakyReLU(0.2), three Conv(4x4, no bias)+BatchNorm+LeakyReLU blocks and
+ * Conv(8 ndf,1,4,s1,p1).  Its convolutions are tv_igemm_nt / tv_wgrad_tn with kh = kw = 4; what follows is everything else.
+ *
+ * First-layer operand: fp32 image [B, 3, H, W] (element strides sn, sc, sh, sw: NCHW-contiguous and channels_last alike) ->
+ * rows [B * H/2 * W/2, 64] bf16, the 4x4 / stride-2 / pad-1 patches in (ky, kx, c) order, column (ky*4 + kx)*3 + c, 48 of 64
+ * used, the rest zero; sigmoid != 0 applies a sigmoid on read (P/transvae/losses/vae_loss.py:80,114-115).  Layer 0 is then a
+ * K = 64 GEMM.  tv_patch4x4s2_bwd is the adjoint in gather form (each pixel sits in at most four patches; no atomics):
+ * drows bf16 -> dimg fp32 [B, 3, H, W] contiguous, times sigmoid'(img) when the flag is set.  H, W even. */
+int tv_patch4x4s2(const float* img, long long sn, long long sc, long long sh, long long sw, void* rows, int B, int H, int W,
+                  int sigmoid, void* stream);
+int tv_patch4x4s2_bwd(const void* drows, const float* img, long long sn, long long sc, long long sh, long long sw, float* dimg,
+                      int B, int H, int W, int sigmoid, void* stream);
+/* BatchNorm2d (training statistics over all M = B*H*W rows) + LeakyReLU(0.2) on rows x [M, C] bf16, C % 8 == 0, C <= 2048.
+ * tv_bn_stats: per-channel sums of (x - piv) and (x - piv)^2 about the pivot piv = x[0][c], one partial per block
+ * (tv_bn_partial_count(M, C) floats of scratch), added in a fixed order in fp64 by a finalise launch: bit-reproducible, no atomics.
+ * Writes mr[0][c] = mean, mr[1][c] = 1 / sqrt(biased variance + eps), ss[0][c] = gamma*rstd, ss[1][c] = beta - mean*gamma*rstd, and
+ * (running_mean / running_var not NULL) running = (1 - momentum) running + momentum {mean, M/(M-1) variance}.
+ * tv_bn_lrelu_apply: y = lrelu(x * ss[0] + ss[1]) -- training forward, its recompute, and eval mode with ss built from the
+ * running statistics.
+ * tv_bn_lrelu_bwd_reduce: red[0][c] = sum dh, red[1][c] = sum dh * xhat with dh = dy * (x*ss[0] + ss[1] > 0 ? 1 : 0.2) and
+ * xhat = (x - mr[0]) * mr[1], same fixed-order scheme; dbeta (+)= red[0], dgamma (+)= red[1] (accumulate != 0 adds).
+ * tv_bn_lrelu_bwd_apply: dx = ss[0] * (dh - (red[0] + xhat red[1]) / M); eval_mode != 0: the plain affine dx = ss[0] * dh. */
+long long tv_bn_partial_count(long long M, int C);
+int tv_bn_stats(const void* x, const float* gamma, const float* beta, float* partials, float* mr, float* ss, float* running_mean,
+                float* running_var, long long M, int C, float eps, float momentum, void* stream);
+int tv_bn_lrelu_apply(const void* x, const float* ss, void* y, long long M, int C, void* stream);
+int tv_bn_lrelu_bwd_reduce(const void* x, const void* dy, const float* mr, const float* ss, float* partials, float* red,
+                           float* dgamma, float* dbeta, long long M, int C, int accumulate, void* stream);
+int tv_bn_lrelu_bwd_apply(const void* x, const void* dy, const float* mr, const float* ss, const float* red, void* dx,
+                          long long M, int C, int eval_mode, void* stream);
+/* GAN loss terms on fp32 logits, value and gradient(s) in one pass.  a: n_a logits, b: n_b logits (NULL / 0 for TV_GAN_GEN).
+ *   TV_GAN_GEN    out = weight * mean bce(a, 1)                          (the generator's term, vae_loss.py:106-111)
+ *   TV_GAN_BCE    out = weight * (mean bce(a, 1) + mean bce(b, 0)) / 2   (a = real, b = fake; vae_loss.py:226-233)
+ *   TV_GAN_HINGE  out = weight * (mean relu(1 - a) + mean relu(1 + b)) / 2
+ *   TV_GAN_WGAN   out = weight * (-mean a + mean b)
+ * bce(x, t) = max(x, 0) - x t + log1p(exp(-|x|)).  da / db (each may be NULL) receive d out / d a, d out / d b.  Block partials
+ * (tv_gan_loss_partial_count(n_a, n_b) floats of scratch, 8-byte aligned: one fp64 partial per block -- the sums are carried in
+ * fp64 from the first add, the wgan form being a difference of means) are added in block order by a finalise launch. */
+#define TV_GAN_GEN 0
+#define TV_GAN_BCE 1
+#define TV_GAN_HINGE 2
+#define TV_GAN_WGAN 3
+long long tv_gan_loss_partial_count(long long n_a, long long n_b);
+int tv_gan_loss(const float* a, const float* b, float* da, float* db, float* partials, float* out, long long n_a, long long n_b,
+                int mode, float weight, void* stream);
 
 #ifdef __cplusplus
 }
