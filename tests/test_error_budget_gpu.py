@@ -3,15 +3,20 @@ the rounding contract implies (checks and references in tests/t
 tests show that these bounds reject specific defects).  Inputs are built to reach where kernels go wrong: per-row scales
 of x over 2^-6..2^6, bias / residual that match or dominate the accumulator, ragged row tails, N edges, forced tiles;
 attention with a large common offset on v, spiked keys and rows whose max grows across the lazy-rescale threshold;
-GroupNorm with |mean| up to 100 std.  Every tuning hook a test sets is restored in a `finally`.
+GroupNorm with |mean| up to 100 std; the production attention branch (fused.AttnBranchFn): rms_ln_hat with |mean u| up to
+100 std u and the fused residual gradient, RoPE in the QKV projection's epilogue across image boundaries, the RoPE adjoint
+in the attention-backward stores.  Every tuning hook a test sets is restored in a `finally`.
 """
 import pytest
 import torch
 
+import functools
+
 from test_error_budget_host import (
-    BF, F64, LSE_C, WGRAD_C, act_grad64, attn_bwd_emul, attn_bwd_exact, attn_exact, attn_fwd_emul, attn_inputs,
-    check_fp32, check_one_rounding, check_vs_emulation, conv64, deriv64, epilogue64, f32, gemm_inputs, gn_inputs,
-    gn_silu64, lse_terms, r16, wgrad64)
+    BF, EPS_LN, EPS_RMS, F64, LSE_C, ROWNORM_C_DW, WGRAD_C, act_grad64, attn_bwd_emul, attn_bwd_exact, attn_exact,
+    attn_fwd_emul, attn_inputs, check_fp32, check_one_rounding, check_vs_emulation, conv64, deriv64, epilogue64, f32,
+    gemm_inputs, gn_inputs, gn_silu64, lse_terms, r16, rms_ln_hat64, rms_ln_inputs, rms_ln_slack, rope_epilogue64,
+    rownorm_bwd64, rownorm_dres, wgrad64)
 
 pytestmark = pytest.mark.gpu
 
@@ -137,6 +142,59 @@ def test_gemm_rows2_against_fp64_of_the_concatenation():
             report(f"[G] rows2 bn={bn}", (tuple(round(v, 3) for v in r1), tuple(round(v, 3) for v in r2)))
     finally:
         lib.tv_set_igemm_config(0, 0, 0, 0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# [G] the QKV projection with RoPE in its epilogue (tv_igemm_nt_rope), as fused.AttnBranchFn launches it
+# ---------------------------------------------------------------------------------------------------------------------------
+ROPE_CASES = [
+    # heads (K = 64 heads, N = 3 K, rope_cols = 2 K), tokens per image, images, table.  rope_cols = 128 (heads 1) and 384
+    # (heads 3) fall inside a 256-wide tile, 128 inside a 192-wide one; M = 420, 900, 300, 600, 360, 1200, 180, 1500 leave a
+    # ragged last row tile and every 128- / 256-row tile of the 60- and 300-token cases straddles an image boundary
+    (1, 60, 7, "indep"), (1, 300, 3, "indep"), (1, 1024, 2, "indep"),
+    (2, 60, 5, "indep"), (2, 300, 2, "indep"), (2, 1024, 3, "real"),
+    (3, 60, 6, "indep"), (3, 300, 4, "indep"), (3, 1024, 2, "indep"),
+    (6, 60, 3, "real"), (6, 300, 5, "indep"), (6, 1024, 2, "indep"),
+]
+_GRID = {60: (5, 12), 300: (15, 20), 1024: (32, 32)}
+
+
+@functools.lru_cache(maxsize=1)
+def _rope_reference(case):
+    heads, tokens, images, table = case
+    M, K = tokens * images, heads * 64
+    x, w, b, _ = gemm_inputs(M, K, 3 * K, seed=M + K)
+    if table == "real":
+        from oracle import filler, transvae_oracle as O
+        tab = torch.stack(O.rope_tables(*_GRID[tokens], filler.inv_freq(64)), 1).float().contiguous()
+    else:
+        tab = _rope_table(tokens, heads)
+    acc, absdot = conv64(x, w, "linear")
+    y64, slack = rope_epilogue64(acc, absdot, b, tab.to(F64), tokens, 2 * K)
+    return x, w, b, tab, y64, slack
+
+
+@pytest.mark.parametrize("cfg", list(TILE_CFGS))
+@pytest.mark.parametrize("case", ROPE_CASES, ids=[f"h{c[0]}-{c[1]}tok-x{c[2]}-{c[3]}" for c in ROPE_CASES])
+def test_rope_epilogue_one_rounding(case, cfg):
+    """[G]: q and k thirds rotated on the fp32 accumulator with the table row of token m % tokens, v third plain, one rounding;
+    tables with four independent planes and the reference's own"""
+    from transvae.hip import _lib as L, ops
+    lib = L.load()
+    heads, tokens, images, _ = case
+    K = heads * 64
+    x, w, b, tab, y64, slack = _rope_reference(case)
+    try:
+        _set_cfg(lib, TILE_CFGS[cfg])
+        y = ops.conv_forward(x.to(dev(), BF), w.float().to(dev()), b.float().to(dev()), None, "linear", L.ACT_NONE, False,
+                             rope=(tab.to(dev()), tokens, 2 * K))[0]
+        torch.cuda.synchronize()
+    finally:
+        _reset_cfg(lib)
+    y = y.cpu()
+    out = {"q,k": check_one_rounding(y[:, :2 * K], y64[:, :2 * K], slack[:, :2 * K], "rotated q, k"),
+           "v": check_one_rounding(y[:, 2 * K:], y64[:, 2 * K:], slack[:, 2 * K:], "v third")}
+    report(f"[G] rope epilogue {case} {cfg} (ratio, max ulps, bias)", {k: tuple(round(v, 3) for v in t) for k, t in out.items()})
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -307,7 +365,9 @@ ATTN_CASES = [
 @pytest.mark.parametrize("case", ATTN_CASES, ids=[f"N{c[0]}-h{c[1]}-{'rope' if c[2] else 'norope'}-{c[3]}" for c in ATTN_CASES])
 def test_attention_against_emulation(case):
     """[A] o and lse of the forward (32-query kernel below 2048 tokens, 64-query kernel from there: key blocks of 64 / 32 in
-    the lazy policy), delta, and dq / dk / dv, per (image, head) slice"""
+    the lazy policy), delta, and dq / dk / dv, per (image, head) slice.  RoPE cases (ragged N = 300, N = 4096): tv_attn_bwd a
+    second time with the table, as the model calls it -- dq, dk against the emulation that applies the adjoint to the fp32
+    sums before the one rounding, dv and delta bit-identical to the run without the table"""
     from transvae.hip import _lib as L
     import ctypes as C
     N, heads, rope, design = case
@@ -339,6 +399,10 @@ def test_attention_against_emulation(case):
     delta = torch.empty(2, 1, heads, N, dtype=torch.float32, device=dev())
     dqkv = torch.empty_like(qkv_d)
     L.check(lib.tv_attn_bwd(p(qkv_d), p(o), p(do_d), p(lse), p(delta), None, p(dqkv), 1, N, heads, 0.125, stream), "tv_attn_bwd")
+    if rope:      # the production form (fused.AttnBranchFn): same rotated q, k; the RoPE adjoint applied in the dq / dk stores
+        delta_t = torch.empty_like(delta)
+        dqkv_t = torch.empty_like(qkv_d)
+        L.check(lib.tv_attn_bwd(p(qkv_d), p(o), p(do_d), p(lse), p(delta_t), p(tab), p(dqkv_t), 1, N, heads, 0.125, stream), "tv_attn_bwd")
     torch.cuda.synchronize()
     qkv_h, o_h, lse_h, dl_h, dqkv_h = qkv_d.cpu().to(F64)[0], o.cpu().to(F64)[0], lse.cpu().to(F64)[0], delta.cpu().to(F64), dqkv.cpu().to(F64)[0]
     kb = 32 if N >= 2048 else 64
@@ -367,6 +431,15 @@ def test_attention_against_emulation(case):
         # the adjoint rotation after tv_attn_bwd)
         for i, nm in enumerate(("dq", "dk", "dv")):
             res[f"{nm} h{h}"] = check_vs_emulation(got[i], em[i], ex[i], f"{nm} head {h}")
+        if rope:
+            tab64, dt = tab.cpu().to(F64), dqkv_t.cpu().to(F64)[0]
+            ex_t = attn_bwd_exact(q, k, v, o_h[:, cs], dox, lse_h[h], 0.125, tab=tab64)
+            em_t = attn_bwd_emul(q, k, v, o_h[:, cs], dox, lse_h[h], 0.125, tab=tab64)
+            got_t = (dt[:, cs], dt[:, Cc + h * 64:Cc + h * 64 + 64], dt[:, 2 * Cc + h * 64:2 * Cc + h * 64 + 64])
+            for i, nm in enumerate(("dq", "dk")):
+                res[f"{nm}+adjoint h{h}"] = check_vs_emulation(got_t[i], em_t[i], ex_t[i], f"{nm} with the adjoint in the store, head {h}")
+            assert torch.equal(got_t[2], got[2]), f"dv head {h} changes with the table"
+            assert torch.equal(delta_t.cpu(), delta.cpu()), "delta changes with the table"
     report(f"[A] {case} (relL2 ratio, max ratio)", {k: tuple(round(v, 3) for v in t) for k, t in res.items()})
 
 
@@ -410,10 +483,62 @@ def test_groupnorm_silu(B, HW, C, G):
     report(f"[N] GroupNorm {B}x{HW}x{C}/{G}", {k: tuple(round(v, 3) for v in t) for k, t in out.items()})
 
 
-@pytest.mark.parametrize("T,Cc", [(300, 384), (2048 + 40, 768), (40, 1536)])
+ROWNORM_LOOP = 8192 + 4 * 2048 + 13     # rows: the forward's 2048 blocks x 4 waves twice and a ragged third pass, the backward's
+                                        # 1024 x 4 four times and a ragged fifth (norm.hip:352,432)
+
+
+def _rownorm_run(x, w, gy, dres, mode, dw0=None):
+    """tv_rownorm_fwd and tv_rownorm_bwd as fused.rownorm_fwd / rownorm_bwd launch them -> (y, dx, dw) on the host; dw starts
+    from dw0 (zeros when None)"""
+    import ctypes as C
+    from transvae.hip import _lib as L
+    lib = L.load()
+    T, Cc = x.shape
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    xd, gd = x.to(dev(), BF).contiguous(), gy.to(dev(), BF).contiguous()
+    wd = w.float().to(dev()).contiguous() if mode == 1 else None
+    rd = dres.to(dev(), BF).contiguous() if dres is not None else None
+    y, dx = torch.empty_like(xd), torch.empty_like(xd)
+    dw = None
+    if mode == 1:
+        dw = torch.zeros(Cc, dtype=torch.float32, device=dev()) if dw0 is None else dw0.float().to(dev()).contiguous()
+    L.check(lib.tv_rownorm_fwd(p(xd), p(wd), p(y), T, Cc, mode, EPS_RMS, EPS_LN, stream), "tv_rownorm_fwd")
+    L.check(lib.tv_rownorm_bwd(p(xd), p(wd), p(gd), p(rd), p(dx), p(dw), T, Cc, mode, EPS_RMS, EPS_LN, stream), "tv_rownorm_bwd")
+    torch.cuda.synchronize()
+    return y.cpu(), dx.cpu(), None if dw is None else dw.cpu()
+
+
+@pytest.mark.parametrize("T,Cc", [(300, 384), (2048 + 40, 768), (40, 1536), (64, 2048), (9, 2560), (ROWNORM_LOOP, 384)])
+def test_rms_ln_hat(T, Cc):
+    """[N] mode 1 (RMSNorm x weight, then the affine-free LayerNorm), the norm of fused.AttnBranchFn: y one rounding; dx one
+    rounding without and with the fused residual gradient; dw fp32 by atomics, three runs (from zero twice, once on top of
+    a running sum).  |mean u| / std u up to 100, an all-zero and a constant row; every per-lane chunk count (C = 384 .. 2560)
+    and the row loop of both kernels taken more than once with a ragged last pass."""
+    x, w, gy = rms_ln_inputs(T, Cc, seed=T + Cc)
+    y64, u, mu, s, _ = rms_ln_hat64(x, w)
+    dres = rownorm_dres(rownorm_bwd64(x, w, gy, None, 1)[0], seed=T)
+    base = f32(torch.randn(Cc, generator=torch.Generator().manual_seed(5), dtype=F64) * 4)
+    out = {}
+    for tag, dr, dw0 in (("", None, None), ("+dres", dres, None), ("+dres, running dw", dres, base)):
+        y, dx, dw = _rownorm_run(x, w, gy, dr, 1, dw0)
+        assert bool(torch.isfinite(y.float()).all()) and bool(torch.isfinite(dx.float()).all())
+        dx64, dsl, dw64, dwt = rownorm_bwd64(x, w, gy, dr, 1)
+        if not tag:
+            out["y"] = check_one_rounding(y, y64, rms_ln_slack(y64, u, mu, s), "rms_ln_hat")
+        out["dx" + tag] = check_one_rounding(dx, dx64, dsl, "rms_ln_hat dx" + tag)
+        if dw0 is None:
+            out["dw" + tag] = (check_fp32(dw, dw64, dwt, ROWNORM_C_DW, "rms_ln_hat dw" + tag),)
+        else:
+            out["dw" + tag] = (check_fp32(dw, dw0 + dw64, dwt + dw0.abs(), ROWNORM_C_DW, "rms_ln_hat dw" + tag),)
+    report(f"[N] rms_ln_hat {T}x{Cc} (ratio, max ulps, bias)", {k: tuple(round(v, 3) for v in t) for k, t in out.items()})
+
+
+@pytest.mark.parametrize("T,Cc", [(300, 384), (2048 + 40, 768), (40, 1536), (ROWNORM_LOOP, 384)])
 def test_rms_hat(T, Cc):
     """[N] rms_hat: y = x rsqrt(mean x^2 + eps) one rounding (2^-20 |y| for the fp32 sum and rsqrt); dx = r (g - xhat
-    mean(g xhat)) one rounding (2^-19 of the terms)"""
+    mean(g xhat)) one rounding (2^-19 of the terms), and the same with the fused residual gradient as fused.ConvFFNBranchFn
+    passes it (+ 2^-24 |dres|)"""
     from transvae.hip import ops
     g = torch.Generator().manual_seed(T)
     rs = torch.exp2(torch.randint(-6, 7, (T, 1), generator=g).to(F64))
@@ -430,4 +555,8 @@ def test_rms_hat(T, Cc):
     dx64 = r * (gy - y64 * m)
     terms = r * (gy.abs() + y64.abs() * (gy * y64).abs().mean(1, keepdim=True))
     out["dx"] = check_one_rounding(xd.grad.cpu(), dx64, 2.0 ** -19 * terms, "rms_hat dx")
+    dres = rownorm_dres(dx64, seed=T)
+    y2, dx2, _ = _rownorm_run(x, None, gy, dres, 0)
+    assert torch.equal(y2, y.detach().cpu())
+    out["dx+dres"] = check_one_rounding(dx2, dx64 + dres, 2.0 ** -19 * terms + 2.0 ** -24 * dres.abs(), "rms_hat dx + dres")
     report(f"[N] rms_hat {T}x{Cc}", {k: tuple(round(v, 3) for v in t) for k, t in out.items()})

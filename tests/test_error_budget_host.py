@@ -21,6 +21,10 @@ Checks
   attention outputs (check_vs_emulation): per (image, head) slice,
       relL2(hip - exact) <= TAU relL2(emul - exact)   and   max|hip - exact| <= 2 max|emul - exact| + ulp_bf16(max|exact|)
   with `emul` the host model of the ideal kernel (attn_fwd_emul / attn_bwd_emul).
+
+The production attention branch (fused.AttnBranchFn) has its own references here: rms_ln_hat64 / rownorm_bwd64 ([N], mode 1
+and the fused residual gradient), rope_epilogue64 ([G], RoPE on the accumulator of the QKV projection) and the `tab` argument
+of attn_bwd_exact / attn_bwd_emul ([A], the RoPE adjoint in the dq / dk stores), each with its fp32 emulation and mutations.
 """
 import math
 
@@ -264,14 +268,37 @@ def attn_fwd_emul(q, k, v, scale, kblock=64, group=32, order=None, mutate=None):
     return o, lse
 
 
-def attn_bwd_exact(q, k, v, o, do, lse, scale):
+def rope_pairs(t, tab, rows, kind="forward", fp32=False):
+    """The reference's (non-orthogonal) RoPE 2x2 on the 64-wide heads of t [M, n 64], pair p = (t[2p], t[2p+1]) = (a, b), with
+    row rows[m] of tab [tokens, 4, 32] = (c1, s1, c2, s2):
+      forward  y[2p] = a c1 - b s1,   y[2p+1] = a s2 + b c2        (igemm_common.h:302-310)
+      adjoint  a'    = a c1 + b s2,   b'      = -a s1 + b c2       (attention.hip:309-317)
+    fp32: each product and the sum rounded to fp32 (the kernels' arithmetic on their fp32 accumulators)."""
+    rd = f32 if fp32 else (lambda v: v)
+    M = t.shape[0]
+    tp = t.to(F64).reshape(M, -1, 32, 2)
+    a, b = tp[..., 0], tp[..., 1]
+    c1, s1, c2, s2 = (tab.to(F64)[rows, i][:, None, :] for i in range(4))
+    if kind == "forward":
+        ya, yb = rd(rd(a * c1) - rd(b * s1)), rd(rd(a * s2) + rd(b * c2))
+    else:
+        ya, yb = rd(rd(a * c1) + rd(b * s2)), rd(rd(b * c2) - rd(a * s1))
+    return torch.stack([ya, yb], -1).reshape(t.shape)
+
+
+def attn_bwd_exact(q, k, v, o, do, lse, scale, tab=None):
     """fp64 backward of the forward the kernel saved (its bf16 o and fp32 lse): delta = sum(do o), P = exp(s - lse),
-    dS = P (do v^T - delta), dq = scale dS k, dk = scale dS^T q, dv = P^T do"""
+    dS = P (do v^T - delta), dq = scale dS k, dk = scale dS^T q, dv = P^T do.  tab [N, 4, 32]: q, k are the rotated values
+    and dq, dk the gradients of the un-rotated projections (the RoPE adjoint of the query's / the key's token)."""
     q, k, v, o, do, lse = (t.to(F64) for t in (q, k, v, o, do, lse))
     delta = (do * o).sum(1)
     p = torch.exp(q @ k.t() * scale - lse[:, None])
     ds = p * (do @ v.t() - delta[:, None])
-    return scale * ds @ k, scale * ds.t() @ q, p.t() @ do, delta
+    dq, dk = scale * ds @ k, scale * ds.t() @ q
+    if tab is not None:
+        rows = torch.arange(q.shape[0])
+        dq, dk = rope_pairs(dq, tab, rows, "adjoint"), rope_pairs(dk, tab, rows, "adjoint")
+    return dq, dk, p.t() @ do, delta
 
 
 def split3(x):
@@ -283,11 +310,14 @@ def split3(x):
     return d0, d1, d2
 
 
-def attn_bwd_emul(q, k, v, o, do, lse, scale, mutate=None):
+def attn_bwd_emul(q, k, v, o, do, lse, scale, mutate=None, tab=None):
     """[A] the backward kernels' documented policy: delta = fp32 sum of do o; P = exp2(s c2 - lse log2e) in fp32;
     dP - delta accumulated in fp32 from -delta as three bf16 pieces; dS = P (dP - delta) rounded to bf16 for dq and dk,
     P rounded to bf16 for dv; fp32 sums; scale applied to the fp32 sum; one rounding of each output.
-    mutate 'delta1': -delta enters as one bf16 piece."""
+    tab [N, 4, 32]: the RoPE adjoint of the query's (dq) / the key's (dk) token applied in fp32 to the scaled fp32 sums
+    before that one rounding (attention.hip:960-962, 1145-1147).
+    mutate 'delta1': -delta enters as one bf16 piece.  With a table: 'rope_fwd' (the forward rotation in place of the
+    adjoint), 'rope_row32' (table row of token + 32), 'rope_after' (adjoint applied to the rounded dq / dk, rounded again)."""
     q, k, v, o, do = (t.to(F64) for t in (q, k, v, o, do))
     c2 = float(np.float32(scale * LOG2E))
     delta = f32((do * o).sum(1))
@@ -297,10 +327,18 @@ def attn_bwd_emul(q, k, v, o, do, lse, scale, mutate=None):
     nd = sum(split3(-delta)) if mutate != "delta1" else r16(-delta)
     dpm = f32(do @ v.t() + nd[:, None])
     ds = r16(f32(p * dpm))
-    dq = r16(f32(f32(ds @ k) * scale))
-    dk = r16(f32(f32(ds.t() @ q) * scale))
+    dq = f32(f32(ds @ k) * scale)
+    dk = f32(f32(ds.t() @ q) * scale)
+    if tab is not None:
+        rows = torch.arange(q.shape[0])
+        if mutate == "rope_row32":
+            rows = (rows + 32) % tab.shape[0]
+        kind = "forward" if mutate == "rope_fwd" else "adjoint"
+        if mutate == "rope_after":
+            dq, dk = r16(dq), r16(dk)
+        dq, dk = rope_pairs(dq, tab, rows, kind, fp32=True), rope_pairs(dk, tab, rows, kind, fp32=True)
     dv = r16(f32(r16(p).t() @ do))
-    return dq, dk, dv, delta
+    return r16(dq), r16(dk), dv, delta
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -322,6 +360,86 @@ def gn_silu64(x, gamma, beta, G, eps=1e-5):
     sh = beta.to(F64) - (mu.view(B, G, 1) * gamma.to(F64).view(1, G, C // G) * rstd.view(B, G, 1)).reshape(B, 1, C)
     slack = LIP["silu"] * 2.0 ** -22 * ((x * sc).abs() + sh.abs() + z.abs()) + 2.0 ** -20 * z.abs()
     return act64(z, "silu"), slack, z, xh, rstd.view(B, G)
+
+
+EPS_RMS, EPS_LN = 1e-6, 1e-5
+
+
+def rms_hat64(x, eps=EPS_RMS):
+    """[N] mode 0: y = x r, r = rsqrt(mean x^2 + eps) -> (y64, r)"""
+    x = x.to(F64)
+    r = torch.rsqrt((x * x).mean(1, keepdim=True) + eps)
+    return x * r, r
+
+
+def rms_ln_hat64(x, w, eps_rms=EPS_RMS, eps_ln=EPS_LN):
+    """[N] mode 1: RMSNorm x weight, then the affine-free LayerNorm.  r = rsqrt(mean x^2 + eps_rms), u = x r w, mu = mean u,
+    s = rsqrt(var u + eps_ln), y = (u - mu) s -> (y64, u, mu, s, r); differentiable (the backward reference is its autograd)"""
+    x, w = x.to(F64), w.to(F64)
+    r = torch.rsqrt((x * x).mean(1, keepdim=True) + eps_rms)
+    u = x * r * w
+    mu = u.mean(1, keepdim=True)
+    s = torch.rsqrt(((u - mu) ** 2).mean(1, keepdim=True) + eps_ln)
+    return (u - mu) * s, u, mu, s, r
+
+
+def rms_ln_slack(y64, u, mu, s):
+    """[N] y of mode 1: u carries three fp32 roundings and the rsqrt, mu an fp32 sum, both enter (u - mu) s; |y64| is s's own
+    relative error"""
+    return 2.0 ** -20 * (s * (u.abs() + mu.abs()) + y64.abs())
+
+
+def rownorm_bwd64(x, w, gy, dres, mode):
+    """[N] backward of rms_hat (mode 0, w ignored) / rms_ln_hat (mode 1) by fp64 autograd, + dres ->
+    (dx64, dx slack, dw64 | None, dw terms | None).
+    terms = the backward formula on absolute values:  du = s (g - mean g - y mean(g y)),  dw = sum_t du xhat,  gx = du w,
+    dx = r (gx - xhat mean(gx xhat)).
+    dx slack: mode 0  2^-19 terms + 2^-24 |dres|;  mode 1  2^-19 terms (1 + |mu| s) + 2^-20 |dx64| + 2^-24 |dres|  (the
+    conditioning factor: y = (u - mu) s is recomputed in fp32, its error is 2^-24 (|u| + |mu|) s).
+    dw terms: sum_t |du xhat| (1 + |mu| s)."""
+    x64 = x.to(F64).clone().requires_grad_(True)
+    w64 = w.to(F64).clone().requires_grad_(True) if mode == 1 else None
+    y = rms_ln_hat64(x64, w64)[0] if mode == 1 else rms_hat64(x64)[0]
+    y.backward(gy.to(F64))
+    dx64 = x64.grad if dres is None else x64.grad + dres.to(F64)
+    x, gy = x.to(F64), gy.to(F64)
+    xh, r = rms_hat64(x)
+    mean = lambda t: t.mean(1, keepdim=True)
+    if mode == 1:
+        y, _, mu, s, _ = rms_ln_hat64(x, w)
+        cond = 1 + mu.abs() * s
+        du = s * (gy - mean(gy) - y * mean(gy * y))
+        g_abs = s * (gy.abs() + mean(gy.abs()) + y.abs() * mean((gy * y).abs())) * w.to(F64).abs()
+        dw_terms = ((du * xh).abs() * cond).sum(0)
+    else:
+        cond, g_abs, dw_terms = 1.0, gy.abs(), None
+    terms = r * (g_abs + xh.abs() * mean(g_abs * xh.abs()))
+    slack = 2.0 ** -19 * terms * cond + (2.0 ** -20 * dx64.abs() if mode == 1 else 0)
+    if dres is not None:
+        slack = slack + 2.0 ** -24 * dres.to(F64).abs()
+    return dx64, slack, (w64.grad if mode == 1 else None), dw_terms
+
+
+def rope_epilogue64(acc, absdot, bias, tab, tokens, rope_cols):
+    """[G] the QKV projection with RoPE on its fp32 accumulator: z = acc + bias; columns < rope_cols (whole 64-wide heads) are
+    rotated pair by pair with table row m % tokens (rope_pairs), the others are the plain projection -> (y64, slack).
+    Slack of a rotated element a c - b s:  2^-20 (absdot_a |c| + absdot_b |s|)  (accumulation)  + 2^-24 (|bias_a c| +
+    |bias_b s|)  (bias add)  + 2^-23 (|a c| + |b s|)  (the two products and their sum); epilogue64's on the others."""
+    z, slack, _ = epilogue64(acc, absdot, bias)
+    M = z.shape[0]
+    rows = torch.arange(M) % tokens
+    y = z.clone()
+    y[:, :rope_cols] = rope_pairs(z[:, :rope_cols], tab, rows)
+    atab = tab.to(F64).abs()
+
+    def fwd_mag(t):          # (|a| |c1| + |b| |s1|, |a| |s2| + |b| |c2|) of the pairs of t
+        tp = t[:, :rope_cols].abs().reshape(M, -1, 32, 2)
+        c1, s1, c2, s2 = (atab[rows, i][:, None, :] for i in range(4))
+        return torch.stack([tp[..., 0] * c1 + tp[..., 1] * s1, tp[..., 0] * s2 + tp[..., 1] * c2], -1).reshape(M, rope_cols)
+    bterm = fwd_mag(bias.to(F64).expand_as(z)) if bias is not None else 0
+    slack = slack.clone()
+    slack[:, :rope_cols] = 2.0 ** -20 * fwd_mag(absdot) + 2.0 ** -24 * bterm + 2.0 ** -23 * fwd_mag(z)
+    return y, slack
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -630,3 +748,271 @@ def test_groupnorm_one_pass_variance_is_rejected():
     check_one_rounding(gn_kernel_emul(x, gamma, beta, G), y64, slack, "clean GroupNorm + SiLU")
     with pytest.raises(AssertionError):
         check_one_rounding(gn_kernel_emul(x, gamma, beta, G, one_pass=True), y64, slack, "one-pass variance")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# [N] row norms: rms_hat (mode 0) and rms_ln_hat (mode 1), forward and backward with the fused residual gradient
+# ---------------------------------------------------------------------------------------------------------------------------
+def rms_ln_inputs(T, C, seed=0):
+    """x [T, C] bf16 values, w [C] fp32 values, gy [T, C] bf16 values.  Per-row scales 2^-6 .. 2^6; a per-row common offset
+    (along 1 / w, so that it survives the weight) that puts |mean u| / std u around 0 (rows 0 mod 3), 4-8 (1 mod 3) and
+    32-100 (2 mod 3): the LayerNorm's cancellation.  Row 1 is all zero and row 2 constant."""
+    g = torch.Generator().manual_seed(seed)
+    w = f32(1 + 0.1 * torch.randn(C, generator=g, dtype=F64))
+    rs = torch.exp2(torch.randint(-6, 7, (T, 1), generator=g).to(F64))
+    u01 = torch.rand(T, 1, generator=g, dtype=F64)
+    kind = (torch.arange(T) % 3)[:, None]
+    off = torch.where(kind == 0, torch.zeros_like(u01), torch.where(kind == 1, 4 + 4 * u01, 32 * (100 / 32) ** u01))
+    off = off * torch.where(torch.rand(T, 1, generator=g) < 0.5, -1.0, 1.0)
+    x = (torch.randn(T, C, generator=g, dtype=F64) + off / w) * rs
+    x[1] = 0
+    x[2] = rs[2] * 3
+    gy = r16(torch.randn(T, C, generator=g, dtype=F64))
+    return r16(x), w, gy
+
+
+def rownorm_dres(dx64, seed=0):
+    """the fused residual gradient of the tests: on even rows of the magnitude of dx and partly cancelling it, on odd rows
+    unrelated unit noise"""
+    g = torch.Generator().manual_seed(seed)
+    n = torch.randn(dx64.shape, generator=g, dtype=F64)
+    even = (torch.arange(dx64.shape[0]) % 2 == 0)[:, None]
+    return r16(torch.where(even, dx64 * (0.5 * n - 1), n))
+
+
+def rownorm_fwd_emul(x, w, mode, mutate=None):
+    """fp32 in the kernel's order of operations (norm.hip:352-404): ss = sum x^2, r = rsqrt(ss / C + eps); mode 1:
+    u = (x r) w, mu = sum u / C, s = rsqrt(sum (u - mu)^2 / C + eps), y = bf16((u - mu) s); mode 0: y = bf16(x r).
+    mutate 'u_bf16': u rounded to bf16 between the two norms."""
+    xf = x.float()
+    inv_c = torch.tensor(1.0 / x.shape[1], dtype=torch.float32)
+    r = torch.rsqrt((xf * xf).sum(1, keepdim=True) * inv_c + EPS_RMS)
+    if mode == 0:
+        return r16(xf * r)
+    u = xf * r * w.float()
+    if mutate == "u_bf16":
+        u = u.to(BF).float()
+    mu = u.sum(1, keepdim=True) * inv_c
+    d = u - mu
+    s = torch.rsqrt((d * d).sum(1, keepdim=True) * inv_c + EPS_LN)
+    return r16(d * s)
+
+
+def rownorm_bwd_emul(x, w, gy, dres, mode, mutate=None, reorder=False):
+    """fp32 in the kernel's order of operations (norm.hip:432-537) -> (dx, dw | None).  xhat = x r; mode 1: u = xhat w, mu, s
+    as in the forward, y = (u - mu) s, du = s (g - mean g - y mean(g y)), dw += du xhat, g := du w; then
+    dx = bf16(r (g - xhat mean(g xhat)) + dres).  The row sum of dw is in no fixed order in the kernel (per-lane chains over a
+    block's rows, LDS atomics over its waves, global atomics over the blocks): `reorder` sums 37 interleaved row classes as
+    sequential fp32 chains and adds them last to first, instead of torch's one fp32 sum.
+    mutate 'dres_after': dres added after the rounding of dx (a second rounding); 'dw_drop_row': one row missing from dw."""
+    xf, g = x.float(), gy.float()
+    inv_c = torch.tensor(1.0 / x.shape[1], dtype=torch.float32)
+    sum_ = lambda t: t.sum(1, keepdim=True)
+    r = torch.rsqrt(sum_(xf * xf) * inv_c + EPS_RMS)
+    xh = xf * r
+    dw = None
+    if mode == 1:
+        wf = w.float()
+        mu = sum_(xh * wf) * inv_c
+        d = xh * wf - mu
+        s = torch.rsqrt(sum_(d * d) * inv_c + EPS_LN)
+        yv = d * s
+        a1, a2 = sum_(g) * inv_c, sum_(g * yv) * inv_c
+        du = s * (g - a1 - yv * a2)
+        c = du * xh
+        if mutate == "dw_drop_row":
+            c = torch.cat([c[:5], c[6:]])
+        if reorder:
+            parts = [torch.from_numpy(np.cumsum(c[i::37].numpy(), axis=0, dtype=np.float32)[-1]) for i in range(min(37, c.shape[0]))]
+            dw = torch.zeros_like(parts[0])
+            for p in reversed(parts):
+                dw = dw + p
+        else:
+            dw = c.sum(0)
+        g = du * wf
+    a3 = sum_(g * xh) * inv_c
+    dx = r * (g - xh * a3)
+    if dres is None:
+        return r16(dx), dw
+    if mutate == "dres_after":
+        return r16(r16(dx) + dres.to(F64)), dw
+    return r16(dx + dres.float()), dw
+
+
+ROWNORM_C_DW = 64.0     # [N] fp32 dw by atomics: the constant of dgamma / dbeta
+ROWNORM_HOST_SHAPES = [(520, 384), (300, 1536), (64, 2048)]
+
+
+def test_rms_ln_inputs_reach_the_cancellation_classes():
+    """the input design does what its docstring says: |mean u| / std u below 0.5, in 3-10 and in 25-130 on the three row
+    classes (rows 1 and 2, the zero and the constant row, aside)"""
+    x, w, _ = rms_ln_inputs(300, 384, seed=1)
+    _, u, mu, s, _ = rms_ln_hat64(x, w)
+    ratio = (mu.abs() * s)[3:, 0]
+    kind = torch.arange(3, 300) % 3
+    assert ratio[kind == 0].max() < 0.5
+    assert 3 < ratio[kind == 1].min() and ratio[kind == 1].max() < 10
+    assert 25 < ratio[kind == 2].min() and ratio[kind == 2].max() < 130
+    assert float(x[1].abs().max()) == 0 and float(x[2].min()) == float(x[2].max()) != 0
+
+
+@pytest.mark.parametrize("T,C", ROWNORM_HOST_SHAPES)
+def test_rms_ln_hat_forward_clean_passes_and_bf16_u_is_rejected(T, C):
+    """[N] mode 1 forward.  Measured here: the clean fp32 emulation at ratio 0.500-0.501 of the bound, rounding bias within
+    +-0.002 ulp; u rounded to bf16 between the two norms lands at 10^3 x the bound (rows at |mean u| / std u of 32-100)."""
+    x, w, _ = rms_ln_inputs(T, C, seed=T + C)
+    y64, u, mu, s, _ = rms_ln_hat64(x, w)
+    slack = rms_ln_slack(y64, u, mu, s)
+    y = rownorm_fwd_emul(x, w, 1)
+    assert bool(torch.isfinite(y).all())
+    rep = check_one_rounding(y, y64, slack, "clean rms_ln_hat")
+    print(f"[error-budget-host] rms_ln_hat {T}x{C} clean (ratio, ulps, bias): {tuple(round(v, 4) for v in rep)}")
+    with pytest.raises(AssertionError):
+        check_one_rounding(rownorm_fwd_emul(x, w, 1, mutate="u_bf16"), y64, slack, "u rounded to bf16")
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+@pytest.mark.parametrize("T,C", ROWNORM_HOST_SHAPES)
+def test_rownorm_backward_clean_passes_and_defects_are_rejected(T, C, mode):
+    """[N] backward of both modes, with and without dres; dw (mode 1) in two summation orders and on top of a running sum.
+    Measured here for the clean fp32 emulation (never the kernel): dx at ratio 0.500-0.52 of its bound in both modes with and
+    without dres; dw at most 0.02 of its bound in either order.  Rejected: dres added after the rounding of dx; dw without
+    one row's contribution."""
+    x, w, gy = rms_ln_inputs(T, C, seed=T + C + mode)
+    dx0, _, _, _ = rownorm_bwd64(x, w, gy, None, mode)
+    dres = rownorm_dres(dx0, seed=T)
+    for dr in (None, dres):
+        dx64, slack, dw64, dw_terms = rownorm_bwd64(x, w, gy, dr, mode)
+        dx, dw = rownorm_bwd_emul(x, w, gy, dr, mode)
+        assert bool(torch.isfinite(dx).all())
+        rep = check_one_rounding(dx, dx64, slack, f"clean rownorm dx mode {mode}")
+        print(f"[error-budget-host] rownorm bwd {T}x{C} mode {mode} dres={dr is not None} dx (ratio, ulps, bias): "
+              f"{tuple(round(v, 4) for v in rep)}")
+    with pytest.raises(AssertionError):
+        check_one_rounding(rownorm_bwd_emul(x, w, gy, dres, mode, mutate="dres_after")[0], dx64, slack, "dres after the rounding")
+    if mode == 1:
+        _, dw2 = rownorm_bwd_emul(x, w, gy, dres, mode, reorder=True)
+        r1 = check_fp32(dw, dw64, dw_terms, ROWNORM_C_DW, "clean dw")
+        r2 = check_fp32(dw2, dw64, dw_terms, ROWNORM_C_DW, "clean dw, reordered")
+        base = f32(torch.randn(C, generator=torch.Generator().manual_seed(5), dtype=F64) * dw64.abs().mean())
+        r3 = check_fp32(f32(base + dw2.to(F64)), base + dw64, dw_terms + base.abs(), ROWNORM_C_DW, "clean dw on a running sum")
+        print(f"[error-budget-host] rownorm dw {T}x{C} ratios: {r1:.4f} {r2:.4f} {r3:.4f}")
+        _, bad = rownorm_bwd_emul(x, w, gy, dres, mode, mutate="dw_drop_row")
+        with pytest.raises(AssertionError):
+            check_fp32(bad, dw64, dw_terms, ROWNORM_C_DW, "dw missing a row")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# [G] RoPE in the epilogue of the QKV projection
+# ---------------------------------------------------------------------------------------------------------------------------
+def rope_table(N, seed):
+    """[N, 4, 32] fp32 values with four independent planes (cos / sin of two unrelated angles): the reference's rotation is
+    not orthogonal, so nothing may rely on c2 = c1, s2 = s1"""
+    g = torch.Generator().manual_seed(seed)
+    ang = torch.rand(N, 32, generator=g) * 6.28
+    return torch.stack([torch.cos(ang), torch.sin(ang), torch.cos(ang * 0.5), torch.sin(ang * 0.5)], 1).contiguous()
+
+
+def rope_kernel_emul(x, w, b, tab, tokens, rope_cols, mutate=None, reverse=False):
+    """fp32 accumulation, + bias, the rotation in fp32 (each product and the sum rounded), one rounding.  Mutations:
+    'after_rounding' (z rounded to bf16, rotated, rounded again), 'plane1' (s2, c2 taken from s1, c1), 'row_m' (table row m
+    instead of m % tokens: `tab` then holds a row for every m), 'v_rot32' (the first 32 columns of the v third rotated too)."""
+    xs, ws = (x.flip(1), w.flip(1)) if reverse else (x, w)
+    z = f32((xs.float() @ ws.float().t()).to(F64) + b)
+    M = z.shape[0]
+    rows = torch.arange(M) if mutate == "row_m" else torch.arange(M) % tokens
+    t = tab.to(F64)
+    if mutate == "plane1":
+        t = torch.stack([t[:, 0], t[:, 1], t[:, 0], t[:, 1]], 1)
+    if mutate == "after_rounding":
+        z = r16(z)
+    y = z.clone()
+    y[:, :rope_cols] = rope_pairs(z[:, :rope_cols], t, rows, fp32=True)
+    if mutate == "v_rot32":
+        full = rope_pairs(z[:, rope_cols:rope_cols + 64], t, rows, fp32=True)
+        y[:, rope_cols:rope_cols + 32] = full[:, :32]
+    return r16(y)
+
+
+@pytest.fixture(scope="module")
+def rope_case():
+    """300 x 192 x 384 (two heads each of q, k and v; columns 0..255 rotated), 60 tokens per image: five images"""
+    M, K, N, tokens, cols = 300, 192, 384, 60, 256
+    x, w, b, _ = gemm_inputs(M, K, N, seed=21)
+    tab_m = rope_table(M, 4).to(F64)            # a row for every m; the clean table is its first `tokens` rows
+    acc, absdot = conv64(x, w, "linear")
+    y64, slack = rope_epilogue64(acc, absdot, b, tab_m[:tokens], tokens, cols)
+    return x, w, b, tab_m, tokens, cols, y64, slack
+
+
+def test_rope_epilogue_clean_emulation_passes_in_both_summation_orders(rope_case):
+    """Measured here: ratio 0.500, rounding bias within +-0.002 ulp; the v third equals the plain projection's reference"""
+    x, w, b, tab_m, tokens, cols, y64, slack = rope_case
+    acc, absdot = conv64(x, w, "linear")
+    plain, _, _ = epilogue64(acc, absdot, b)
+    assert torch.equal(plain[:, cols:], y64[:, cols:]) and not torch.equal(plain[:, :cols], y64[:, :cols])
+    for rev in (False, True):
+        rep = check_one_rounding(rope_kernel_emul(x, w, b, tab_m[:tokens], tokens, cols, reverse=rev), y64, slack, f"clean rope reverse={rev}")
+        print(f"[error-budget-host] rope epilogue clean reverse={rev} (ratio, ulps, bias): {tuple(round(v, 4) for v in rep)}")
+
+
+@pytest.mark.parametrize("mutation", ["after_rounding", "plane1", "row_m", "v_rot32"])
+def test_rope_epilogue_mutations_are_rejected(rope_case, mutation):
+    """rotation after the rounding; s2 / c2 taken from s1 / c1; table row m instead of m % tokens (wrong from the second image
+    on); rotation applied to the first 32 columns of the v third"""
+    x, w, b, tab_m, tokens, cols, y64, slack = rope_case
+    tab = tab_m if mutation == "row_m" else tab_m[:tokens]
+    y = rope_kernel_emul(x, w, b, tab, tokens, cols, mutate=mutation)
+    if mutation == "row_m":       # the first image is right: the defect is only visible behind an image boundary
+        check_one_rounding(y[:tokens], y64[:tokens], slack[:tokens], "first image", min_bias_n=10 ** 9)
+    with pytest.raises(AssertionError):
+        check_one_rounding(y, y64, slack, mutation)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# [A] attention backward with the RoPE adjoint in its stores
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def attn_rope_case():
+    N = 256
+    q, k, v = attn_inputs(N, seed=8, v_offset=4.0)
+    g = torch.Generator().manual_seed(9)
+    do = r16(torch.randn(N, 64, generator=g, dtype=F64))
+    tab = rope_table(N, 6).to(F64)
+    o, lse = attn_fwd_emul(q, k, v, 0.125)
+    ex = attn_bwd_exact(q, k, v, o, do, lse, 0.125, tab=tab)
+    clean = attn_bwd_emul(q, k, v, o, do, lse, 0.125, tab=tab)
+    return (q, k, v, o, do, lse, tab), ex, clean
+
+
+def test_attention_backward_rope_adjoint_reference_is_the_adjoint(attn_rope_case):
+    """<R x, g> == <x, R^T g> in fp64 for rope_pairs; without a table the extended functions return what they did; dv does
+    not depend on the table"""
+    (q, k, v, o, do, lse, tab), ex, clean = attn_rope_case
+    g = torch.Generator().manual_seed(2)
+    xx, gg = torch.randn(256, 128, generator=g, dtype=F64), torch.randn(256, 128, generator=g, dtype=F64)
+    rows = torch.arange(256)
+    lhs = (rope_pairs(xx, tab, rows) * gg).sum()
+    rhs = (xx * rope_pairs(gg, tab, rows, "adjoint")).sum()
+    assert abs(lhs - rhs) <= 1e-12 * (xx.abs() * gg.abs()).sum()
+    ex0 = attn_bwd_exact(q, k, v, o, do, lse, 0.125)
+    em0 = attn_bwd_emul(q, k, v, o, do, lse, 0.125)
+    assert torch.equal(ex0[2], ex[2]) and torch.equal(em0[2], clean[2])
+    assert torch.equal(rope_pairs(ex0[0], tab, rows, "adjoint"), ex[0])
+    for i, nm in enumerate(("dq", "dk", "dv")):
+        check_vs_emulation(clean[i], clean[i], ex[i], nm)
+
+
+@pytest.mark.parametrize("mutation", ["rope_fwd", "rope_row32"])
+def test_attention_backward_rope_adjoint_mutations_are_rejected(attn_rope_case, mutation):
+    """the forward rotation in place of the adjoint; the table row of token + 32 (a tile-local index): relL2 400-540 x the
+    emulation's.  Not rejected, and so not listed: the adjoint applied after the rounding of dq / dk and rounded again
+    (mutate 'rope_after').  It adds a second rounding of the same size; measured on three slices (N = 256 with and without
+    the offset on v, N = 300) its relL2 is 1.16-1.23 x the emulation's and its max error 0.25-0.42 of that rule, which
+    straddles TAU = 1.2.  TAU is calibrated by test_tau_calibration_from_two_orderings and stays; what holds the adjoint
+    store to a single rounding is the element-by-element one-rounding contract of rows G / D, which row A does not have."""
+    args, ex, clean = attn_rope_case
+    bad = attn_bwd_emul(*args[:6], 0.125, mutate=mutation, tab=args[6])
+    for i, nm in ((0, "dq"), (1, "dk")):
+        with pytest.raises(AssertionError):
+            check_vs_emulation(bad[i], clean[i], ex[i], f"{nm} {mutation}")

@@ -138,6 +138,7 @@ CHUNK_CASES = [
     ("c3up", (3, 8, 8, 64), (96, 3, 3), "silu", True),
     ("unshuf", (4, 8, 12, 64), (128, 2, 2), None, True),
     ("shuf", (3, 6, 5, 128), (256, 1, 1), None, False),
+    ("rope", (6 * 64, 64), (192,), None, False),             # the QKV projection with RoPE in its epilogue: 6 images of 8 x 8 tokens
 ]
 
 
@@ -149,6 +150,25 @@ def test_launches_in_batch_chunks_equal_one_launch(case, monkeypatch):
     bit-identical to the single launch (images are independent) and the weight / bias gradients equal to fp32 summation order."""
     from transvae.hip import ops
     mode, xs, ws, act, use_res = case
+    if mode == "rope":
+        # ops.conv_forward(rope=...): chunks start on image boundaries (align = tokens per image), so every chunk indexes the
+        # table from its own row 0; forward only (its backward is attention's), output bit-identical to the single launch
+        from transvae.hip import _lib
+        x, w, b = _mk("linear", xs, ws, seed=91)
+        tokens, cols = 64, 2 * xs[1]
+        tab = _rope_tab(8, 8).to(dev())
+        fwd = lambda: ops.conv_forward(x.to(dev(), BF), w.to(dev()), b.to(dev()), None, "linear", _lib.ACT_NONE, False,
+                                       rope=(tab, tokens, cols))[0]
+        one = fwd()
+        monkeypatch.setattr(ops, "_LAUNCH_BYTES", ws[0] * 2 * (xs[0] // 2) + 1)   # at most half of the rows per launch
+        ch = ops._batch_chunks(xs[0], (x.to(BF), one), align=tokens)
+        assert ch is not None and len(ch) >= 2 and all(s0 % tokens == 0 and c0 % tokens == 0 for s0, c0 in ch)
+        many = fwd()
+        torch.cuda.synchronize()
+        assert torch.equal(one, many)
+        plain = ops.conv_forward(x.to(dev(), BF), w.to(dev()), b.to(dev()), None, "linear", _lib.ACT_NONE, False)[0]
+        assert rel(many[:, cols:], plain[:, cols:]) < 1e-2 and not torch.equal(many[:, :cols], plain[:, :cols])
+        return
     x, w, b = _mk(mode, xs, ws, seed=91)
 
     def run():
