@@ -9,15 +9,18 @@ dict of `lpips.LPIPS(net='vgg')` with `PerceptualLoss.from_file` (INTEGRATION.md
 reference's configs) is `TransVAELoss(use_gan=True)` handed a discriminator, `DiscriminatorLoss` for the discriminator's own
 objective, and `PatchDiscriminator` (transvae/models/discriminator.py), the 70x70 PatchGAN on the HIP path, trained from
 scratch.  The VF term needs DINOv2's trained weights and is out of scope.  The evaluation side (R/evaluate.py) is `evaluate` with per-image
-PSNR / SSIM / MSE from `reconstruction_metrics` (transvae/metrics.py) and LPIPS from a `PerceptualLoss`, computed on the device.
+PSNR / SSIM / MSE from `reconstruction_metrics` (transvae/metrics.py), LPIPS from a `PerceptualLoss` and rFID from an
+`InceptionFeatures` (the FID Inception-v3 on the HIP path, transvae/metrics_fid.py; weights loaded from the pt_inception file)
+with a `FrechetDistance`, computed on the device.
 """
 from .evaluate import evaluate
 from .losses.lpips import PerceptualLoss
 from .losses.vae_loss import DiscriminatorLoss, TransVAELoss
 from .metrics import reconstruction_metrics
+from .metrics_fid import FrechetDistance, InceptionFeatures
 from .models.discriminator import PatchDiscriminator
 from .models.transvae import TransVAE, create_transvae
 
 __version__ = "0.2.0"
 __all__ = ["TransVAE", "create_transvae", "TransVAELoss", "reconstruction_metrics", "evaluate", "PerceptualLoss", "DiscriminatorLoss",
-           "PatchDiscriminator"]
+           "PatchDiscriminator", "InceptionFeatures", "FrechetDistance"]

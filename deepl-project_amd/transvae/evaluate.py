@@ -4,7 +4,9 @@ The reference copies every batch to the host and runs skimage one image at a tim
 :func:`transvae.metrics.reconstruction_metrics` on the device (the reference's definitions: inputs clipped to [0, 1],
 skimage's 7x7 SSIM, data_range 1), stay there while the loop runs and reach the host once, at the end.  LPIPS follows
 R/evaluate.py:126-133: `lpips(images * 2 - 1, reconstruction * 2 - 1)` on the UNCLIPPED tensors, original first, from the
-`PerceptualLoss` handed in as `lpips_net`.
+`PerceptualLoss` handed in as `lpips_net`.  rFID (the `rfid` of the reference's configs) is the Frechet distance between the
+FID Inception-v3 features of the originals and of the reconstructions, both clipped to [0, 1], from the `InceptionFeatures`
+handed in as `fid_net`; the feature statistics stream through a `FrechetDistance` on the device (transvae/metrics_fid.py).
 """
 from __future__ import annotations
 
@@ -19,7 +21,8 @@ _KNOWN = ("psnr", "ssim", "mse")
 
 
 def evaluate(model: torch.nn.Module, dataloader: Iterable, metrics: Sequence[str] = ("psnr", "ssim"),
-             device="cuda", per_image: bool = False, lpips_net: Optional[torch.nn.Module] = None) -> Dict[str, Dict]:
+             device="cuda", per_image: bool = False, lpips_net: Optional[torch.nn.Module] = None,
+             fid_net: Optional[torch.nn.Module] = None) -> Dict[str, Dict]:
     """{metric: {"mean", "std", "median"}} over every image of `dataloader`, like R/evaluate.py.
 
     `dataloader` yields `(images, labels)` pairs as in the reference (a bare image tensor is accepted too).  The model runs
@@ -27,16 +30,26 @@ def evaluate(model: torch.nn.Module, dataloader: Iterable, metrics: Sequence[str
     (P/evaluate_transvae.py:134).  The statistics are NumPy's over the per-image values taken as float64 (`np.std` is the
     population standard deviation).  "lpips" needs `lpips_net`, a `transvae.PerceptualLoss` with loaded weights on `device`
     (the package ships none); without one it raises ValueError.  per_image=True (not in the reference) adds each metric's
-    per-image values, in loader order, as a float64 array under "values".
+    per-image values, in loader order, as a float64 array under "values".  "rfid" needs `fid_net`, a
+    `transvae.InceptionFeatures` with loaded weights on `device`; it is a property of the whole set, so its entry is
+    {"value", "n"} (n images per side) and per_image adds nothing to it.
     """
     metrics = tuple(metrics)
     if "lpips" in metrics and lpips_net is None:
         raise ValueError("evaluate (HIP path): the LPIPS term needs the external VGG network's weights, which this package neither "
                          "ships nor fetches; pass lpips_net=PerceptualLoss.from_file(...) or drop 'lpips' from metrics")
-    unknown = [m for m in metrics if m not in _KNOWN and m != "lpips"]
+    if "rfid" in metrics and fid_net is None:
+        raise ValueError("evaluate (HIP path): rFID needs the FID Inception-v3 weights, which this package neither ships nor "
+                         "fetches; pass fid_net=InceptionFeatures.from_file(...) or drop 'rfid' from metrics")
+    unknown = [m for m in metrics if m not in _KNOWN and m not in ("lpips", "rfid")]
     if unknown or not metrics:
-        raise ValueError(f"evaluate: unknown metrics {unknown} (expected a non-empty subset of {list(_KNOWN) + ['lpips']})")
+        raise ValueError(f"evaluate: unknown metrics {unknown} (expected a non-empty subset of {list(_KNOWN) + ['lpips', 'rfid']})")
     model.eval()
+    frechet = None
+    if "rfid" in metrics:
+        from .metrics_fid import FrechetDistance
+        frechet = FrechetDistance()
+    metrics_all, metrics = metrics, tuple(m for m in metrics if m != "rfid")
     values = {m: [] for m in metrics}
     with torch.no_grad():
         for batch in dataloader:
@@ -48,6 +61,10 @@ def evaluate(model: torch.nn.Module, dataloader: Iterable, metrics: Sequence[str
                 batch_values = reconstruction_metrics(reconstruction, images, ssim_window="skimage", transform="clip", data_range=1.0)
             if "lpips" in metrics:
                 batch_values["lpips"] = lpips_net(images, reconstruction, normalize=True).reshape(-1)
+            if frechet is not None:      # originals and reconstructions as one batch of 2B
+                nb = images.shape[0]
+                feats = fid_net.features(images, reconstruction, clip=True)
+                frechet.update(feats[:nb], feats[nb:])
             for m in metrics:
                 values[m].append(batch_values[m])
     results = {}
@@ -56,4 +73,7 @@ def evaluate(model: torch.nn.Module, dataloader: Iterable, metrics: Sequence[str
         results[m] = {"mean": float(np.mean(v)), "std": float(np.std(v)), "median": float(np.median(v))}
         if per_image:
             results[m]["values"] = v
+    if frechet is not None:
+        results["rfid"] = {"value": frechet.compute(), "n": frechet.n[0]}
+        results = {m: results[m] for m in metrics_all}
     return results

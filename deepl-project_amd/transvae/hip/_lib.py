@@ -24,6 +24,7 @@ ACTX_RELU = 5                       # TV_ACTX_RELU: desc.act of a ReLU layer; as
 ACTX_LRELU = 6                      # TV_ACTX_LRELU: LeakyReLU(0.2), same rules as ACTX_RELU (the PatchGAN discriminator)
 GAN_GEN, GAN_BCE, GAN_HINGE, GAN_WGAN = 0, 1, 2, 3   # tv_gan_loss modes
 LPIPS_MAP, LPIPS_SIGMOID, LPIPS_CLAMP = 1, 2, 4   # tv_lpips_prep flags
+POOL3_MAX_S2, POOL3_MAX_S1P1, POOL3_AVG_S1P1 = 0, 1, 2   # tv_pool3x3 modes
 SSIM_SKIMAGE, SSIM_BOX11 = 0, 1                 # tv_recon_metrics window kinds
 METRIC_NONE, METRIC_CLIP, METRIC_SIGMOID = 0, 1, 2   # tv_recon_metrics input transforms
 DERIVE_UP_FWD, DERIVE_UP_DGRAD, DERIVE_UP_WGRAD_FOLD, DERIVE_S2_PARITY = 1, 2, 3, 4   # tv_conv3x3_derived forms
@@ -99,6 +100,12 @@ SIGNATURES = {
     "tv_bn_lrelu_bwd_apply": (_I, [_P, _P, _P, _P, _P, _P, _LL, _I, _I, _P]),
     "tv_gan_loss_partial_count": (_LL, [_LL, _LL]),
     "tv_gan_loss": (_I, [_P, _P, _P, _P, _P, _P, _LL, _LL, _I, _F, _P]),
+    "tv_fid_prep": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "tv_pool3x3": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "tv_gather_line": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "tv_global_avgpool": (_I, [_P, _P, _I, _I, _I, _P]),
+    "tv_fid_state_doubles": (_LL, [_I]),
+    "tv_fid_accumulate": (_I, [_P, _I, _I, _I, _LL, _P, _P, _P]),
 }
 
 _lib = None

@@ -13,6 +13,8 @@ Layer "modes" of :class:`ConvFn` (geometry table in include/transvae_hip.h):
     c3up    nearest-x2 upsample + Conv2d 3x3     (upsample.py:94-95), upsample never materialised
     unshuf  pixel_unshuffle(2) + 1x1             (upsample.py:60-61)  == 2x2 / stride-2 conv
     shuf    1x1 + pixel_shuffle(2)               (upsample.py:121-123) == GEMM with shuffled store
+    c3v1 / c3v2 / c5s1 / c1   Conv2d 3x3 unpadded at stride 1 / 2, 5x5 pad 2, 1x1 on NHWC: forward only (the frozen FID
+                              Inception-v3 of transvae/metrics_fid.py; conv_dgrad raises on them)
 """
 from __future__ import annotations
 
@@ -422,6 +424,14 @@ class _Geo:
             elif mode == "c4s1":   # 4x4 / stride 1 / pad 1: the grid shrinks by one (odd grids occur)
                 _require(self.H >= 2 and self.W >= 2, "operand check failed: self.H >= 2 and self.W >= 2")
                 self.Ho, self.Wo = self.H - 1, self.W - 1
+            elif mode == "c3v1":   # 3x3 / stride 1 / no padding (the Inception stem): forward only, like the three modes below
+                _require(self.H >= 3 and self.W >= 3, "operand check failed: self.H >= 3 and self.W >= 3")
+                self.Ho, self.Wo = self.H - 2, self.W - 2
+            elif mode == "c3v2":   # 3x3 / stride 2 / no padding, floor
+                _require(self.H >= 3 and self.W >= 3, "operand check failed: self.H >= 3 and self.W >= 3")
+                self.Ho, self.Wo = (self.H - 3) // 2 + 1, (self.W - 3) // 2 + 1
+            elif mode in ("c5s1", "c1"):   # 5x5 / stride 1 / pad 2; 1x1 on an NHWC tensor
+                self.Ho, self.Wo = self.H, self.W
             elif mode == "shuf":
                 _require(self.KH == 1 and self.KW == 1 and self.Cout % 4 == 0, "operand check failed: self.KH == 1 and self.KW == 1 and self.Cout % 4 == 0")
                 self.Ho, self.Wo = self.H, self.W          # GEMM grid; stored to [B,2H,2W,Cout/4]
@@ -433,7 +443,7 @@ class _Geo:
                 self.out_shape = (self.B, self.Ho, self.Wo, self.Cout)
         _require(w.shape[-1] == self.Cin, "operand check failed: " + repr((mode, tuple(x.shape), tuple(w.shape))))
         exp_k = {"linear": (1, 1), "c3s1": (3, 3), "c3s2": (3, 3), "c3up": (3, 3), "unshuf": (2, 2), "shuf": (1, 1), "c4s2": (4, 4),
-                 "c4s1": (4, 4)}[mode]
+                 "c4s1": (4, 4), "c3v1": (3, 3), "c3v2": (3, 3), "c5s1": (5, 5), "c1": (1, 1)}[mode]
         _require((self.KH, self.KW) == exp_k, "operand check failed: " + repr((mode, tuple(w.shape))))
 
     def fwd_desc(self, act: int) -> L.ConvDesc:
@@ -455,6 +465,14 @@ class _Geo:
             return _desc(**common, stride=2, pad=1)
         if m == "c4s1":
             return _desc(**common, stride=1, pad=1)
+        if m == "c3v1":
+            return _desc(**common, stride=1, pad=0)
+        if m == "c3v2":
+            return _desc(**common, stride=2, pad=0)
+        if m == "c5s1":
+            return _desc(**common, stride=1, pad=2)
+        if m == "c1":
+            return _desc(**common)
         if m == "shuf":
             common["ldo"] = self.Cout // 4
             return _desc(**common, store_shuffle=1)

@@ -414,6 +414,42 @@ long long tv_gan_loss_partial_count(long long n_a, long long n_b);
 int tv_gan_loss(const float* a, const float* b, float* da, float* db, float* partials, float* out, long long n_a, long long n_b,
                 int mode, float weight, void* stream);
 
+/* rFID: everything of the FID Inception-v3 pool3 extractor that is not a convolution, and the Frechet statistics (csrc/fid.hip) --
+ * The network is the FID literature's Inception-v3 (pt_inception / pytorch-fid FIDInceptionV3): input in [0, 1], bilinear resize
+ * to 299 x 299 (align_corners=False, no antialiasing), 2x - 1, 94 bias-free convolutions with eval-mode BatchNorm (folded into
+ * the bf16 weight and an fp32 bias at pack time) and ReLU -- tv_igemm_nt launches with TV_ACTX_RELU --, 3x3 pools, global
+ * average pool -> [B, 2048] fp32.  Activations bf16 NHWC.
+ *
+ * tv_fid_prep: fp32 NCHW images a [Ba, 3, H, W] and b [Bb, 3, H, W] (b may be NULL with Bb = 0), H, W >= 8 -> cols
+ * [Ba + Bb, 149, 149, 32] bf16: the 3x3 / stride-2 / unpadded patches ((ky, kx, c) order, 27 of 32 columns used, the rest zero)
+ * of the resized, 2x - 1 mapped image, i.e. the operand of the first convolution as a K = 32 GEMM.  clip != 0 clamps the source
+ * pixels to [0, 1] first.  The interpolation weights are exact fractions rounded once to fp32. */
+int tv_fid_prep(const float* a, const float* b, void* cols, int Ba, int Bb, int H, int W, int clip, void* stream);
+/* 3x3 pools, x [B, H, W, C] bf16 -> y [B, Ho, Wo, *] with row stride ldo >= C (a column range of a wider tensor), C % 8 == 0:
+ *   TV_POOL3_MAX_S2     max, stride 2, no padding, Ho = (H - 3) / 2 + 1       (bit-equal to F.max_pool2d(x, 3, 2))
+ *   TV_POOL3_MAX_S1P1   max, stride 1, pad 1                                  (bit-equal to F.max_pool2d(x, 3, 1, 1))
+ *   TV_POOL3_AVG_S1P1   average, stride 1, pad 1, divided by the number of in-bounds taps (count_include_pad=False): fp32 sum in
+ *                       tap order, one IEEE division, one rounding to bf16 */
+#define TV_POOL3_MAX_S2 0
+#define TV_POOL3_MAX_S1P1 1
+#define TV_POOL3_AVG_S1P1 2
+int tv_pool3x3(const void* x, void* y, int B, int H, int W, int C, int ldo, int mode, void* stream);
+/* Row gather along one axis: x [B, H, W, C] bf16 -> y [B * H * W, taps * C] bf16 with
+ * y[(b, i, j), t, c] = x[b, i + t - taps / 2, j, c] (axis 0) or x[b, i, j + t - taps / 2, c] (axis 1), zero outside the image.
+ * taps is 3 or 7, C % 8 == 0.  A 1 x taps / taps x 1 "same" convolution is then a GEMM with K = taps * C (the descriptor of
+ * tv_igemm_nt has one pad for both axes and cannot express it). */
+int tv_gather_line(const void* x, void* y, int B, int H, int W, int C, int taps, int axis, void* stream);
+/* Global average pool: x [B, HW, C] bf16 -> out [B, C] fp32; pixels summed in order in fp64, one rounding.  C % 8 == 0. */
+int tv_global_avgpool(const void* x, float* out, int B, int HW, int C, void* stream);
+/* Streaming first and second moments of feature rows, fp64 on the device.
+ * state: tv_fid_state_doubles(D) doubles (-1: D must be a multiple of 64 up to 8192), zero-initialised by the caller:
+ * {count, unused, mean[D], M2[D * D]}, M2 the centred scatter matrix sum (x - mean)(x - mean)^T.  x [B, D] fp32 with row stride ldx;
+ * n0 = the number of rows merged so far (the caller keeps it; state[0] mirrors it); scratch: B * D doubles.
+ * The rows are merged one at a time, in order, by the pairwise (Chan) merge with a single sample (Welford's update), so the
+ * state after N rows is the same bits however the rows were cut into calls, and independent of the launch geometry. */
+long long tv_fid_state_doubles(int D);
+int tv_fid_accumulate(const float* x, int B, int D, int ldx, long long n0, double* state, double* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
