@@ -538,6 +538,79 @@ __global__ __launch_bounds__(256) void rownorm_bwd_kernel(const bf16* __restrict
     }
 }
 
+// Plain LayerNorm over token rows (the DINOv2 ViT of csrc/vf.hip): one wave per row, the row in registers, TWO-pass statistics
+// (mean, then the sum of squared deviations from it -- a residual stream whose rows sit far from 0 would cancel in E[x^2] - mean^2).
+//   FINAL = false (tv_rownorm_fwd mode 2): y = bf16((x - mean) rstd), affine-free -- the affine is folded into the next projection
+//   FINAL = true  (tv_layernorm_rows):     y = fp32 (x - mean) rstd gamma + beta on rows skip .. n_tok-1 of every image only,
+//                                          stored densely [B, n_tok - skip, C]
+template <int KCH, bool FINAL>
+__global__ __launch_bounds__(256) void layernorm_rows_kernel(const bf16* __restrict__ x, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, bf16* __restrict__ y16, float* __restrict__ y32,
+                                                             int T, int C, int n_tok, int skip, float eps) {
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int nch = C >> 3;
+    const float inv_c = 1.0f / (float)C;
+    for (int row = blockIdx.x * 4 + wave; row < T; row += gridDim.x * 4) {
+        int src = row;
+        if constexpr (FINAL) {
+            const int per = n_tok - skip;
+            const int b = row / per;
+            src = b * n_tok + skip + (row - b * per);
+        }
+        const bf16* xr = x + (size_t)src * C;
+        float v[KCH][8];
+        float su = 0.f;
+#pragma unroll
+        for (int k = 0; k < KCH; ++k) {
+            const int ch = lane + 64 * k;
+            bf16x8 t = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (ch < nch) t = *(const bf16x8*)(xr + ch * 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                v[k][e] = (float)t[e];
+                su += v[k][e];
+            }
+        }
+        const float mu = tv_wave_sum(su) * inv_c;
+        float sv = 0.f;
+#pragma unroll
+        for (int k = 0; k < KCH; ++k) {
+            const int ch = lane + 64 * k;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                v[k][e] = (ch < nch) ? v[k][e] - mu : 0.f;
+                sv = fmaf(v[k][e], v[k][e], sv);
+            }
+        }
+        const float s = rsqrtf(tv_wave_sum(sv) * inv_c + eps);
+#pragma unroll
+        for (int k = 0; k < KCH; ++k) {
+            const int ch = lane + 64 * k;
+            if (ch < nch) {
+                if constexpr (FINAL) {
+                    float* yr = y32 + (size_t)row * C + ch * 8;
+                    const f32x4 g0 = *(const f32x4*)(gamma + ch * 8), g1 = *(const f32x4*)(gamma + ch * 8 + 4);
+                    const f32x4 b0 = *(const f32x4*)(beta + ch * 8), b1 = *(const f32x4*)(beta + ch * 8 + 4);
+                    f32x4 o0, o1;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        o0[e] = fmaf(v[k][e] * s, g0[e], b0[e]);
+                        o1[e] = fmaf(v[k][e + 4] * s, g1[e], b1[e]);
+                    }
+                    *(f32x4*)yr = o0;
+                    *(f32x4*)(yr + 4) = o1;
+                } else {
+                    bf16x8 o;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) o[e] = (bf16)(v[k][e] * s);
+                    *(bf16x8*)(y16 + (size_t)row * C + ch * 8) = o;
+                }
+            }
+        }
+    }
+}
+
 }  // namespace
 
 // ---- C ABI ------------------------------------------------------------------------------------
@@ -634,9 +707,16 @@ extern "C" int tv_rownorm_fwd(const void* x, const float* w, void* y, int T, int
                               void* stream) {
     TV_CHECK_ARG(x && y && T > 0, "tv_rownorm_fwd: null pointer / empty");
     TV_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 64 * 8 * RN_MAXCH, "tv_rownorm_fwd: C=%d must be a multiple of 8 and <= 2560", C);
-    TV_CHECK_ARG(mode == 0 || (mode == 1 && w), "tv_rownorm_fwd: mode %d (mode 1 needs w)", mode);
+    TV_CHECK_ARG(mode == 0 || (mode == 1 && w) || mode == 2, "tv_rownorm_fwd: mode %d (mode 1 needs w)", mode);
     const int grid = min(tv_cdiv(T, 4), 256 * 8);
     const int kch = tv_cdiv(C >> 3, 64);      // 16-byte chunks per lane
+    if (mode == 2) {
+#define TV_LN_FWD(K) hipLaunchKernelGGL((layernorm_rows_kernel<K, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, nullptr, nullptr, (bf16*)y, nullptr, T, C, 1, 0, eps_ln)
+        if (kch <= 1) TV_LN_FWD(1); else if (kch == 2) TV_LN_FWD(2); else if (kch == 3) TV_LN_FWD(3); else TV_LN_FWD(5);
+#undef TV_LN_FWD
+        TV_CHECK_LAUNCH("tv_rownorm_fwd");
+        return TV_OK;
+    }
 #define TV_RN_FWD(M, K) hipLaunchKernelGGL((rownorm_fwd_kernel<M, K>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, w, (bf16*)y, T, C, eps_rms, eps_ln)
     if (mode == 0) {
         if (kch <= 1) TV_RN_FWD(0, 1); else if (kch == 2) TV_RN_FWD(0, 2); else if (kch == 3) TV_RN_FWD(0, 3); else TV_RN_FWD(0, 5);
@@ -645,6 +725,22 @@ extern "C" int tv_rownorm_fwd(const void* x, const float* w, void* y, int T, int
     }
 #undef TV_RN_FWD
     TV_CHECK_LAUNCH("tv_rownorm_fwd");
+    return TV_OK;
+}
+
+extern "C" int tv_layernorm_rows(const void* x, const float* gamma, const float* beta, float* y, int B, int n_tok, int skip, int C, float eps,
+                                 void* stream) {
+    TV_CHECK_ARG(x && gamma && beta && y && B > 0 && n_tok > 0 && skip >= 0 && skip < n_tok, "tv_layernorm_rows: bad arguments (B=%d n_tok=%d skip=%d)",
+                 B, n_tok, skip);
+    TV_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 64 * 8 * RN_MAXCH, "tv_layernorm_rows: C=%d must be a multiple of 8 and <= 2560", C);
+    TV_CHECK_ARG((long long)B * n_tok < (1ll << 31), "tv_layernorm_rows: too many rows");
+    const int T = B * (n_tok - skip);
+    const int grid = min(tv_cdiv(T, 4), 256 * 8);
+    const int kch = tv_cdiv(C >> 3, 64);
+#define TV_LN_FIN(K) hipLaunchKernelGGL((layernorm_rows_kernel<K, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, gamma, beta, nullptr, y, T, C, n_tok, skip, eps)
+    if (kch <= 1) TV_LN_FIN(1); else if (kch == 2) TV_LN_FIN(2); else if (kch == 3) TV_LN_FIN(3); else TV_LN_FIN(5);
+#undef TV_LN_FIN
+    TV_CHECK_LAUNCH("tv_layernorm_rows");
     return TV_OK;
 }
 

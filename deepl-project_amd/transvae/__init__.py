@@ -8,7 +8,9 @@ implicit-GEMM kernels as the model, max-pools and the LPIPS head in csrc/lpips.h
 dict of `lpips.LPIPS(net='vgg')` with `PerceptualLoss.from_file`.  The adversarial stage (stage 2 of the
 reference's configs) is `TransVAELoss(use_gan=True)` handed a discriminator, `DiscriminatorLoss` for the discriminator's own
 objective, and `PatchDiscriminator` (transvae/models/discriminator.py), the 70x70 PatchGAN on the HIP path, trained from
-scratch.  The VF term needs DINOv2's trained weights and is out of scope.  The evaluation side (R/evaluate.py) is `evaluate` with per-image
+scratch.  The VF alignment term (stage 1 of the reference's configs: L1 + LPIPS + KL + VF) is `TransVAELoss(vf_loss=VFLoss(...))`
+handed a `DinoV2Features` as `dinov2`: the DINOv2 ViT patch-feature extractor on the HIP path (transvae/losses/vf.py, csrc/vf.hip;
+weights loaded with `DinoV2Features.from_file`, none ship) and the cosine head with its gradient into the latent.  The evaluation side (R/evaluate.py) is `evaluate` with per-image
 PSNR / SSIM / MSE from `reconstruction_metrics` (transvae/metrics.py), LPIPS from a `PerceptualLoss` and rFID from an
 `InceptionFeatures` (the FID Inception-v3 on the HIP path, transvae/metrics_fid.py; weights loaded from the pt_inception file)
 with a `FrechetDistance`, computed on the device.
@@ -16,6 +18,7 @@ with a `FrechetDistance`, computed on the device.
 from .evaluate import evaluate
 from .losses.lpips import PerceptualLoss
 from .losses.vae_loss import DiscriminatorLoss, TransVAELoss
+from .losses.vf import DinoV2Features, VFLoss
 from .metrics import reconstruction_metrics
 from .metrics_fid import FrechetDistance, InceptionFeatures
 from .models.discriminator import PatchDiscriminator
@@ -23,4 +26,4 @@ from .models.transvae import TransVAE, create_transvae
 
 __version__ = "0.2.0"
 __all__ = ["TransVAE", "create_transvae", "TransVAELoss", "reconstruction_metrics", "evaluate", "PerceptualLoss", "DiscriminatorLoss",
-           "PatchDiscriminator", "InceptionFeatures", "FrechetDistance"]
+           "PatchDiscriminator", "InceptionFeatures", "FrechetDistance", "VFLoss", "DinoV2Features"]

@@ -106,6 +106,14 @@ SIGNATURES = {
     "tv_global_avgpool": (_I, [_P, _P, _I, _I, _I, _P]),
     "tv_fid_state_doubles": (_LL, [_I]),
     "tv_fid_accumulate": (_I, [_P, _I, _I, _I, _LL, _P, _P, _P]),
+    "tv_vf_prep": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "tv_vit_tokens": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "tv_layernorm_rows": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "tv_vf_head_partial_count": (_LL, [_I]),
+    "tv_vf_head": (_I, [_P] * 9 + [_I] * 7 + [_F, _P]),
+    "tv_vf_head_dproj_partial_count": (_LL, [_I, _I, _I]),
+    "tv_vf_head_dproj": (_I, [_P] * 9 + [_I, _I, _I, _P]),
+    "tv_bilinear_nchw_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
 }
 
 _lib = None

@@ -4,8 +4,9 @@ Interface mirror of R/transvae/losses/vae_loss.py (`TransVAELoss(l1_weight, lpip
 use_gan)`, `forward(reconstruction, target, mu, logvar, discriminator=None, dinov2=None) -> dict` with keys 'l1', 'kl', 'total').
 The LPIPS term (vae_loss.py:86-91) is computed by a `PerceptualLoss` (transvae/losses/lpips.py, VGG-16 on the HIP path) handed in
 as `lpips_net`; its pretrained weights are not part of this package and cannot be fetched by it, so a non-zero lpips_weight
-WITHOUT an lpips_net raises.  VF (DINOv2) needs another network's trained weights -- out of scope; asking for it
-raises.  The GAN term (vae_loss.py:103-111) takes the caller's discriminator -- `transvae.PatchDiscriminator` on the HIP path,
+WITHOUT an lpips_net raises.  The VF term (vae_loss.py:99-101) is computed by a `VFLoss` handed in as `vf_loss` when forward() is
+given a `DinoV2Features` as `dinov2` (transvae/losses/vf.py: the DINOv2 ViT and the head on the HIP path; weights loaded by the
+caller); a `dinov2` without a `vf_loss`, or one that is not a `DinoV2Features`, raises.  The GAN term (vae_loss.py:103-111) takes the caller's discriminator -- `transvae.PatchDiscriminator` on the HIP path,
 or any module returning logits -- and `DiscriminatorLoss` (vae_loss.py:199-244) is the discriminator's own objective; both
 run through `tv_gan_loss`, value and gradients in one pass.  The two closed-form terms are
 
@@ -130,12 +131,14 @@ class DiscriminatorLoss(nn.Module):
 class TransVAELoss(nn.Module):
     def __init__(self, l1_weight: float = 1.0, lpips_weight: float = 1.0, kl_weight: float = 1e-8, vf_weight: float = 0.1,
                  gan_weight: float = 0.05, use_gan: bool = False, sigmoid_recon: bool = False, kl_mean: bool = False,
-                 logvar_clip: Optional[Tuple[float, float]] = None, lpips_net: Optional[nn.Module] = None):
+                 logvar_clip: Optional[Tuple[float, float]] = None, lpips_net: Optional[nn.Module] = None,
+                 vf_loss: Optional[nn.Module] = None):
         """Defaults are the reference's (R/transvae/losses/vae_loss.py:31-38: lpips 1.0, vf 0.1, gan 0.05, use_gan False), so
         `TransVAELoss()` cannot silently mean something else here: the LPIPS term (always on in the reference, which fetches
         the VGG weights from the network) needs `lpips_net`, a `transvae.PerceptualLoss` with loaded weights; a non-zero
         lpips_weight without one RAISES -- pass lpips_weight=0 for the closed-form terms alone.  The VF term only exists in
-        the reference when its forward() is handed a DINOv2 model (vae_loss.py:99-101); handing one to this forward() raises.
+        the reference when its forward() is handed a DINOv2 model (vae_loss.py:99-101); here it needs `vf_loss`, a
+        `transvae.VFLoss`, and a `transvae.DinoV2Features` handed to forward() -- any other `dinov2` raises.
         The GAN term exists, as in the reference, when use_gan is set AND forward() is handed a discriminator
         (vae_loss.py:103-111)."""
         super().__init__()
@@ -147,11 +150,16 @@ class TransVAELoss(nn.Module):
         self.vf_weight, self.gan_weight, self.use_gan = vf_weight, gan_weight, use_gan
         self.sigmoid_recon, self.kl_mean, self.logvar_clip = sigmoid_recon, kl_mean, logvar_clip
         self.lpips_net = lpips_net if lpips_weight != 0.0 else None   # a submodule: moves with .to(); buffers only, no parameters
+        self.vf_loss = vf_loss                                        # a submodule as well; its `proj` is an ordinary parameter
 
     def forward(self, reconstruction, target, mu, logvar, discriminator=None, dinov2=None) -> dict:
+        vf = None
         if dinov2 is not None and self.vf_weight > 0:
-            raise ValueError("TransVAELoss (HIP path): the VF (DINOv2) term is outside this build; call without dinov2 and add "
-                             "that term with the reference's own module")
+            from .vf import DinoV2Features
+            if self.vf_loss is None or not isinstance(dinov2, DinoV2Features):
+                raise ValueError("TransVAELoss (HIP path): the VF (DINOv2) term needs vf_loss=transvae.VFLoss(...) at construction and a "
+                                 "transvae.DinoV2Features as dinov2; call without dinov2, or add that term with the reference's own module")
+            vf = self.vf_loss(reconstruction, target, mu, dinov2) * self.vf_weight      # (vae_loss.py:99-101)
         out = fused_l1_kl(reconstruction, target, mu, logvar, self.l1_weight, self.kl_weight, self.kl_mean, self.sigmoid_recon,
                           self.logvar_clip)
         gan = None
@@ -159,17 +167,29 @@ class TransVAELoss(nn.Module):
             # gan_weight * BCE_with_logits(D(reconstruction), ones) (vae_loss.py:103-111); the patched copy feeds the
             # discriminator sigmoid(reconstruction) and only when gan_weight > 0 (P/.../vae_loss.py:114-115)
             gan = self._gan_term(reconstruction, discriminator)
-        if self.lpips_net is None:
+        if self.lpips_net is None and vf is None:
             if gan is None:
                 return {"l1": out[0], "kl": out[1], "total": out[2]}
             return {"l1": out[0], "kl": out[1], "gan": gan, "total": out[0] + out[1] + gan}
-        # lpips_weight * lpips(recon * 2 - 1, target * 2 - 1).mean() (vae_loss.py:86-91); under sigmoid_recon the patched copy's
-        # order: sigmoid, 2x - 1, clamp to [-1, 1] on both images (P/.../vae_loss.py:80-91) -- all inside the network's input pass
-        d = self.lpips_net.distance(reconstruction, target, normalize=True, sigmoid_input=self.sigmoid_recon, clamp=self.sigmoid_recon)
-        lp = d.mean() * self.lpips_weight
-        if gan is None:
-            return {"l1": out[0], "lpips": lp, "kl": out[1], "total": out[0] + lp + out[1]}   # (the reference's sum order)
-        return {"l1": out[0], "lpips": lp, "kl": out[1], "gan": gan, "total": out[0] + lp + out[1] + gan}
+        # the reference's key and sum order: l1, lpips, kl, vf, gan (vae_loss.py:83-114)
+        losses = {"l1": out[0]}
+        total = out[0]
+        if self.lpips_net is not None:
+            # lpips_weight * lpips(recon * 2 - 1, target * 2 - 1).mean() (vae_loss.py:86-91); under sigmoid_recon the patched copy's
+            # order: sigmoid, 2x - 1, clamp to [-1, 1] on both images (P/.../vae_loss.py:80-91) -- all inside the network's input pass
+            d = self.lpips_net.distance(reconstruction, target, normalize=True, sigmoid_input=self.sigmoid_recon, clamp=self.sigmoid_recon)
+            losses["lpips"] = d.mean() * self.lpips_weight
+            total = total + losses["lpips"]
+        losses["kl"] = out[1]
+        total = total + out[1]
+        if vf is not None:
+            losses["vf"] = vf
+            total = total + vf
+        if gan is not None:
+            losses["gan"] = gan
+            total = total + gan
+        losses["total"] = total
+        return losses
 
     def _gan_term(self, reconstruction, discriminator):
         if getattr(discriminator, "takes_sigmoid_flag", False):     # PatchDiscriminator: the sigmoid rides on its input pass

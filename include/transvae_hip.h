@@ -205,6 +205,7 @@ int tv_gn_silu_bwd_apply(const void* x, const void* dy, const void* dres, const 
  * mode 0: y = x * rsqrt(mean(x^2)+eps_rms)                     (RMSNorm, weight folded downstream)
  * mode 1: u = x*w*rsqrt(mean(x^2)+eps_rms); y = (u-mean u)*rsqrt(var u + eps_ln)
  *         (RMSNorm followed by the affine-free LayerNorm shared by norm_q/k/v)
+ * mode 2: y = (x-mean x)*rsqrt(var x + eps_ln)   (plain affine-free LayerNorm, forward only: the frozen ViT of the VF term)
  * rows: x,y [T, C] bf16; w fp32 [C] (mode 1 only). */
 int tv_rownorm_fwd(const void* x, const float* w, void* y, int T, int C, int mode, float eps_rms,
                    float eps_ln, void* stream);
@@ -449,6 +450,42 @@ int tv_global_avgpool(const void* x, float* out, int B, int HW, int C, void* str
  * state after N rows is the same bits however the rows were cut into calls, and independent of the launch geometry. */
 long long tv_fid_state_doubles(int D);
 int tv_fid_accumulate(const float* x, int B, int D, int ldx, long long n0, double* state, double* scratch, void* stream);
+
+/* VF alignment term (R/transvae/losses/vae_loss.py:119-196): the DINOv2 ViT patch-feature extractor's own kernels and the loss
+ * head (csrc/vf.hip; the plain LayerNorm is tv_rownorm_fwd mode 2 and tv_layernorm_rows, csrc/norm.hip) ---------------------
+ * The ViT is facebookresearch/dinov2's DinoVisionTransformer (patch 14, LayerNorm eps 1e-6, LayerScale, erf-GELU MLP): patch
+ * embedding, qkv / proj / fc1 / fc2 are tv_igemm_nt launches, the attention tv_attn_fwd (scale 1/8, no table).
+ *
+ * tv_vf_prep: fp32 NCHW images [B, 3, H, W] -> rows [B * gh * gw, 608] bf16, the 14 x 14 / stride-14 patches ((c, ky, kx) order,
+ * 588 of 608 columns used, the rest zero) of the image resized bilinearly to (14 gh) x (14 gw) (align_corners=False, no
+ * antialiasing; the interpolation weights are exact fractions rounded once) and, imagenet_norm != 0, normalised with the ImageNet
+ * mean / std in fp32 before the one rounding to bf16. */
+int tv_vf_prep(const float* img, void* rows, int B, int H, int W, int gh, int gw, int imagenet_norm, void* stream);
+/* Token assembly: patch [B, n_patch, D] bf16, cls [D] fp32, pos [1 + n_patch, D] fp32 -> tok [B, 1 + n_patch, D] bf16;
+ * row 0 = cls + pos[0], row 1 + p = patch[p] + pos[1 + p], one fp32 sum and one rounding each.  D % 8 == 0. */
+int tv_vit_tokens(const void* patch, const float* cls, const float* pos, void* tok, int B, int n_patch, int D, void* stream);
+/* LayerNorm with its affine on rows skip .. n_tok-1 of every image of x [B, n_tok, C] bf16 -> y [B, n_tok - skip, C] fp32
+ * (two-pass statistics in registers, as tv_rownorm_fwd mode 2: y = (x - mean) rsqrt(var + eps_ln), affine-free, bf16). */
+int tv_layernorm_rows(const void* x, const float* gamma, const float* beta, float* y, int B, int n_tok, int skip, int C, float eps,
+                      void* stream);
+/* VF head, fp32 throughout.  lat [B, D, Hl, Wl] fp32 is sampled bilinearly (align_corners=False) on the gh x gw grid of the
+ * features feat [B * gh * gw, C] fp32 (token-major); y = w z + bias with w [C, D], bias [C] (both NULL: y = z, D == C <= 64;
+ * with a projection D <= 32); per position cos = y . f / (max(|y|, 1e-12) max(|f|, 1e-12)); similarity = mean over all positions
+ * (fp64 sum of tv_vf_head_partial_count(T) block partials, 8-byte aligned, in block order).
+ * out[0] = max(margin - similarity, 0), out[1] = gate (1 when margin - similarity >= 0, else 0), out[2] = similarity.
+ * dzr [T, D] receives d out[0] / d (sampled latent) WITHOUT the gate; zr [T, D] (the sampled latent) and ab [T, 2] are
+ * written when given (both needed by tv_vf_head_dproj).
+ * tv_vf_head_dproj: dw [C, D], db [C] = gate * gradient of out[0] w.r.t. the projection; gate = &out[1]; scratch of
+ * tv_vf_head_dproj_partial_count(T, C, D) floats, slab partials added in slab order.
+ * tv_bilinear_nchw_bwd: dlat [B, D, Hl, Wl] = gate[0] * (adjoint of the bilinear sampling applied to g [B, gh, gw, D]); gate may
+ * be NULL (1).  Every element gathers its contributions in a fixed order: no atomics, the same bits on every run. */
+long long tv_vf_head_partial_count(int T);
+int tv_vf_head(const float* lat, const float* feat, const float* w, const float* bias, void* partials, float* out, float* dzr, float* zr,
+               float* ab, int B, int D, int Hl, int Wl, int gh, int gw, int C, float margin, void* stream);
+long long tv_vf_head_dproj_partial_count(int T, int C, int D);
+int tv_vf_head_dproj(const float* feat, const float* zr, const float* ab, const float* w, const float* bias, const float* gate,
+                     float* partials, float* dw, float* db, int T, int C, int D, void* stream);
+int tv_bilinear_nchw_bwd(const float* g, const float* gate, float* dlat, int B, int D, int Hl, int Wl, int gh, int gw, void* stream);
 
 #ifdef __cplusplus
 }
