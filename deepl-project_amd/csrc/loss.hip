@@ -43,8 +43,12 @@ __global__ __launch_bounds__(LOSS_THREADS) void vae_loss_kernel(const float* __r
             float r = recon[i];
             float dr = 1.f;
             if (sigmoid) {
-                r = 1.f / (1.f + __expf(-r));
-                dr = r * (1.f - r);
+                // sigmoid and its derivative from e = exp(-|r|) in (0, 1]: r (1 - r) cancels where the sigmoid saturates (1e-2
+                // relative at logit 12, 0 from 17 on); e / (1 + e)^2 does not (the form of tv_patch4x4s2_bwd, gan.hip)
+                const float e = expf(-fabsf(r));
+                const float q = 1.f / (1.f + e);
+                r = r >= 0.f ? q : e * q;
+                dr = e * q * q;
             }
             const float d = r - target[i];
             acc += fabsf(d);
@@ -58,15 +62,17 @@ __global__ __launch_bounds__(LOSS_THREADS) void vae_loss_kernel(const float* __r
         for (long long i = start + threadIdx.x; i < end; i += LOSS_THREADS) {
             const float m = mu[i];
             float lv = logvar[i];
-            bool inside = true;
+            bool outside = false;
             if (clamp) {
-                inside = lv >= lv_lo && lv <= lv_hi;
-                lv = fminf(fmaxf(lv, lv_lo), lv_hi);
+                // torch.clamp: a NaN is neither below lo nor above hi and passes through, into the term and the gradient
+                // (fminf / fmaxf return the other operand and would turn it into lo, hiding it from the non-finite guard)
+                outside = lv < lv_lo || lv > lv_hi;
+                lv = lv < lv_lo ? lv_lo : (lv > lv_hi ? lv_hi : lv);
             }
             const float e = __expf(lv);
             acc += -0.5f * (1.f + lv - m * m - e);
             if (d_mu) d_mu[i] = kl_scale * m;
-            if (d_logvar) d_logvar[i] = inside ? kl_scale * -0.5f * (1.f - e) : 0.f;
+            if (d_logvar) d_logvar[i] = outside ? 0.f : kl_scale * -0.5f * (1.f - e);
         }
         acc *= kl_scale;
     }

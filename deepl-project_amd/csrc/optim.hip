@@ -52,20 +52,24 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_sqnorm_kernel(const OptTensor
     const long long end = min(t.numel, start + OPT_CHUNK);
     const float* g = t.grad;
     float acc = 0.f;
-    if ((((uintptr_t)g) & 15) == 0) {
-        const long long n4 = (end - start) >> 2;
-        const f32x4* g4 = (const f32x4*)(g + start);
-        for (long long i = threadIdx.x; i < n4; i += OPT_THREADS) {
-            const f32x4 v = g4[i];
-            acc = fmaf(v[0], v[0], acc);
-            acc = fmaf(v[1], v[1], acc);
-            acc = fmaf(v[2], v[2], acc);
-            acc = fmaf(v[3], v[3], acc);
+    // thread j sums the groups of four j, j + 256, ... and then the tail, whatever the pointer's alignment (an unaligned
+    // gradient only loads its group element by element): the norm, and so the clip coefficient, has the same bits at any address
+    const bool vec = (((uintptr_t)g) & 15) == 0;
+    const long long n4 = (end - start) >> 2;
+    for (long long i = threadIdx.x; i < n4; i += OPT_THREADS) {
+        f32x4 v;
+        if (vec) {
+            v = ((const f32x4*)(g + start))[i];
+        } else {
+            const float* q = g + start + (i << 2);
+            v = f32x4{q[0], q[1], q[2], q[3]};
         }
-        for (long long i = start + (n4 << 2) + threadIdx.x; i < end; i += OPT_THREADS) acc = fmaf(g[i], g[i], acc);
-    } else {
-        for (long long i = start + threadIdx.x; i < end; i += OPT_THREADS) acc = fmaf(g[i], g[i], acc);
+        acc = fmaf(v[0], v[0], acc);
+        acc = fmaf(v[1], v[1], acc);
+        acc = fmaf(v[2], v[2], acc);
+        acc = fmaf(v[3], v[3], acc);
     }
+    for (long long i = start + (n4 << 2) + threadIdx.x; i < end; i += OPT_THREADS) acc = fmaf(g[i], g[i], acc);
     const float s = block_sum(acc, s_red);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
