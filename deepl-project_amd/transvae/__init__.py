@@ -13,9 +13,14 @@ handed a `DinoV2Features` as `dinov2`: the DINOv2 ViT patch-feature extractor on
 weights loaded with `DinoV2Features.from_file`, none ship) and the cosine head with its gradient into the latent.  The evaluation side (R/evaluate.py) is `evaluate` with per-image
 PSNR / SSIM / MSE from `reconstruction_metrics` (transvae/metrics.py), LPIPS from a `PerceptualLoss` and rFID from an
 `InceptionFeatures` (the FID Inception-v3 on the HIP path, transvae/metrics_fid.py; weights loaded from the pt_inception file)
-with a `FrechetDistance`, computed on the device.
+with a `FrechetDistance`, computed on the device.  The image pipeline (transvae/image_io.py, csrc/image.hip): `ImagePrep` is the
+scripts' `Resize -> CenterCrop -> ToTensor` for a ragged uint8 batch (`collate_uint8` / `UInt8Batch`) in one launch, bit-equal to
+PIL; `to_uint8_grid` / `save_image` stand in for torchvision's `make_grid` / `save_image`; transvae/generate.py holds the three
+modes of P/generate_images.py.
 """
 from .evaluate import evaluate
+from .generate import interpolate_latents, random_samples, reconstruct
+from .image_io import ImagePrep, UInt8Batch, collate_uint8, save_image, to_uint8_grid
 from .losses.lpips import PerceptualLoss
 from .losses.vae_loss import DiscriminatorLoss, TransVAELoss
 from .losses.vf import DinoV2Features, VFLoss
@@ -26,4 +31,5 @@ from .models.transvae import TransVAE, create_transvae
 
 __version__ = "0.2.0"
 __all__ = ["TransVAE", "create_transvae", "TransVAELoss", "reconstruction_metrics", "evaluate", "PerceptualLoss", "DiscriminatorLoss",
-           "PatchDiscriminator", "InceptionFeatures", "FrechetDistance", "VFLoss", "DinoV2Features"]
+           "PatchDiscriminator", "InceptionFeatures", "FrechetDistance", "VFLoss", "DinoV2Features", "ImagePrep", "UInt8Batch",
+           "collate_uint8", "to_uint8_grid", "save_image", "random_samples", "interpolate_latents", "reconstruct"]

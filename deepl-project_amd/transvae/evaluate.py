@@ -20,9 +20,26 @@ from .metrics import reconstruction_metrics
 _KNOWN = ("psnr", "ssim", "mse")
 
 
+def _uint8_images(batch, device):
+    """The images of one batch of a uint8 loader, on the device: a tuple is (images, labels); a list of two whose first entry
+    is itself a batch (UInt8Batch, list or 4-D tensor) is the default collate's form of such a tuple; any other list is the
+    images themselves."""
+    from .image_io import UInt8Batch
+    if isinstance(batch, tuple):
+        batch = batch[0]
+    elif isinstance(batch, list) and len(batch) == 2 and (isinstance(batch[0], (UInt8Batch, list))
+                                                          or (isinstance(batch[0], torch.Tensor) and batch[0].dim() == 4)):
+        batch = batch[0]
+    if isinstance(batch, (UInt8Batch, torch.Tensor)):
+        return batch.to(device, non_blocking=True)
+    if isinstance(batch, list):
+        return [im.to(device, non_blocking=True) if isinstance(im, torch.Tensor) else im for im in batch]
+    return batch
+
+
 def evaluate(model: torch.nn.Module, dataloader: Iterable, metrics: Sequence[str] = ("psnr", "ssim"),
              device="cuda", per_image: bool = False, lpips_net: Optional[torch.nn.Module] = None,
-             fid_net: Optional[torch.nn.Module] = None) -> Dict[str, Dict]:
+             fid_net: Optional[torch.nn.Module] = None, prep=None) -> Dict[str, Dict]:
     """{metric: {"mean", "std", "median"}} over every image of `dataloader`, like R/evaluate.py.
 
     `dataloader` yields `(images, labels)` pairs as in the reference (a bare image tensor is accepted too).  The model runs
@@ -33,6 +50,12 @@ def evaluate(model: torch.nn.Module, dataloader: Iterable, metrics: Sequence[str
     per-image values, in loader order, as a float64 array under "values".  "rfid" needs `fid_net`, a
     `transvae.InceptionFeatures` with loaded weights on `device`; it is a property of the whole set, so its entry is
     {"value", "n"} (n images per side) and per_image adds nothing to it.
+
+    `prep` (a `transvae.image_io.ImagePrep`): the loader yields decoded uint8 images -- a `UInt8Batch` (from `collate_uint8`), a
+    list of uint8 HWC images of mixed sizes or a dense uint8 [B, H, W, 3] tensor, bare or as the first element of an
+    `(images, labels)` tuple -- and each batch goes through `prep` on the device before the model, replacing the reference's
+    per-image `Resize -> CenterCrop -> ToTensor` on the host (R/evaluate.py:39-42).  The reference's 256 / 512 / 1024 benchmark is
+    then three calls over one uint8 loader.  Without `prep` nothing changes.
     """
     metrics = tuple(metrics)
     if "lpips" in metrics and lpips_net is None:
@@ -53,8 +76,11 @@ def evaluate(model: torch.nn.Module, dataloader: Iterable, metrics: Sequence[str
     values = {m: [] for m in metrics}
     with torch.no_grad():
         for batch in dataloader:
-            images = batch[0] if isinstance(batch, (tuple, list)) else batch
-            images = images.to(device)
+            if prep is not None:
+                images = prep(_uint8_images(batch, device))
+            else:
+                images = batch[0] if isinstance(batch, (tuple, list)) else batch
+                images = images.to(device)
             reconstruction = model(images)[0]
             batch_values = {}
             if any(m in _KNOWN for m in metrics):

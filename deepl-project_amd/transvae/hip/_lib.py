@@ -27,6 +27,8 @@ LPIPS_MAP, LPIPS_SIGMOID, LPIPS_CLAMP = 1, 2, 4   # tv_lpips_prep flags
 POOL3_MAX_S2, POOL3_MAX_S1P1, POOL3_AVG_S1P1 = 0, 1, 2   # tv_pool3x3 modes
 SSIM_SKIMAGE, SSIM_BOX11 = 0, 1                 # tv_recon_metrics window kinds
 METRIC_NONE, METRIC_CLIP, METRIC_SIGMOID = 0, 1, 2   # tv_recon_metrics input transforms
+IMAGE_NONE, IMAGE_SIGMOID = 0, 1                # tv_image_grid_u8 transforms
+ERR_UNSUPPORTED = 4                             # TV_ERR_UNSUPPORTED
 DERIVE_UP_FWD, DERIVE_UP_DGRAD, DERIVE_UP_WGRAD_FOLD, DERIVE_S2_PARITY = 1, 2, 3, 4   # tv_conv3x3_derived forms
 
 
@@ -37,6 +39,12 @@ class ConvDesc(C.Structure):
         "h_out", "w_out", "c_out", "ldo",
         "kh", "kw", "stride", "pad",
         "up_shift", "dil_mask", "act", "store_shuffle")]
+
+
+class ImageDesc(C.Structure):
+    """struct tv_image_desc (include/transvae_hip.h)."""
+    _fields_ = [("offset", C.c_longlong)] + [(n, C.c_int) for n in (
+        "in_h", "in_w", "row_stride", "channels", "out_h", "out_w", "crop_top", "crop_left", "xtab", "xk", "ytab", "yk")]
 
 
 _P, _I, _F, _LL = C.c_void_p, C.c_int, C.c_float, C.c_longlong
@@ -114,6 +122,8 @@ SIGNATURES = {
     "tv_vf_head_dproj_partial_count": (_LL, [_I, _I, _I]),
     "tv_vf_head_dproj": (_I, [_P] * 9 + [_I, _I, _I, _P]),
     "tv_bilinear_nchw_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "tv_image_prep": (_I, [_P, _LL, _P, _P, _I, _P, _P, _LL, _P, _P, _I, _I, _P]),
+    "tv_image_grid_u8": (_I, [_P, _LL, _LL, _LL, _LL, _P, _I, _I, _I, _I, _I, _F, _I, _P]),
 }
 
 _lib = None

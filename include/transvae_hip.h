@@ -30,7 +30,8 @@ extern "C" {
 #define TV_ERR_ARG 1     /* bad shape / unsupported configuration */
 #define TV_ERR_LAUNCH 2  /* HIP reported a launch error */
 #define TV_ERR_INIT 3    /* no device / allocation of the zero page failed */
-#define TV_ERR_UNSUPPORTED 4 /* tv_igemm_nt_cat2 only: this shape's tile has no two-source loop -- concatenate and call tv_igemm_nt (no error text) */
+#define TV_ERR_UNSUPPORTED 4 /* tv_igemm_nt_cat2: this shape's tile has no two-source loop -- concatenate and call tv_igemm_nt (no error text);
+                                tv_image_prep: an image outside the supported set (error text names it) */
 
 #define TV_ACT_NONE 0
 #define TV_ACT_GELU 1 /* exact (erf) GELU, R/transvae/modules/conv.py:56,86 */
@@ -486,6 +487,45 @@ long long tv_vf_head_dproj_partial_count(int T, int C, int D);
 int tv_vf_head_dproj(const float* feat, const float* zr, const float* ab, const float* w, const float* bias, const float* gate,
                      float* partials, float* dw, float* db, int T, int C, int D, void* stream);
 int tv_bilinear_nchw_bwd(const float* g, const float* gate, float* dlat, int B, int D, int Hl, int Wl, int gh, int gw, void* stream);
+
+/* Image pipeline (csrc/image.hip): decoded uint8 images in, uint8 grids out ------------------------------------------------------
+ * tv_image_prep is torchvision's Resize(res) -> CenterCrop(res) -> ToTensor() as every script of the reference builds it
+ * (R/train.py:141-144,396-399, R/evaluate.py:39-42, R/inference_example.py:13-16, P/generate_images.py:152-155; R/train_2.py:166-170
+ * adds x*2-1) for a ragged batch in ONE launch, bit-equal to PIL's 8-bit bilinear resample: per axis a table of int32 fixed-point
+ * coefficients (22 fraction bits, built on the host in float64 as PIL builds them), horizontal pass first, rounded and clipped to
+ * uint8, then the vertical pass on those uint8 values; each pass is clip((2^21 + sum pixel * k) >> 22, 0, 255).  A pass whose
+ * table index is negative is skipped (a copy; its output size must equal its input size), as PIL skips it.
+ *   src       : device bytes holding the B images, RGB, HWC, uint8; src_bytes = its length
+ *   desc_host / desc_dev : the same B descriptors on the host (checked here before the launch: extents, crop, tables -- the
+ *               kernel indexes nothing that was not checked) and on the device (read by the kernel)
+ *   coef_host / coef_dev : the coefficient tables, coef_len int32 each side.  A table for n output indices (n = res_w for the
+ *               horizontal axis, res_h for the vertical one: only the rows / columns that survive the crop) with `ksize` taps at
+ *               offset t is  first_tap[n], tap_count[n], k[n][ksize]  starting at coef[t]
+ *   lut       : 256 device floats, the value of each byte: float(v) / 255.0f for ToTensor, that * 2 - 1 for the signed range
+ *   out       : fp32 [B, 3, res_h, res_w], NCHW contiguous
+ * Supported: any up-scale, down-scale ratios up to 16 per axis.  A larger ratio, a channel count other than 3 or an empty image
+ * returns TV_ERR_UNSUPPORTED (with error text naming the image); other inconsistencies TV_ERR_ARG.  No device synchronisation. */
+typedef struct tv_image_desc {
+    long long offset;                     /* byte offset of pixel (0, 0) in src; any alignment */
+    int in_h, in_w, row_stride, channels; /* row_stride in bytes, >= 3 * in_w; channels must be 3 */
+    int out_h, out_w;                     /* size after the resize, before the crop */
+    int crop_top, crop_left;              /* the output is rows crop_top .. crop_top + res_h - 1 of the resized image, likewise columns */
+    int xtab, xk;                         /* horizontal table: offset into coef and taps per entry; xtab < 0: pass skipped */
+    int ytab, yk;                         /* vertical table */
+} tv_image_desc;
+int tv_image_prep(const void* src, long long src_bytes, const tv_image_desc* desc_host, const tv_image_desc* desc_dev, int B,
+                  const int* coef_host, const int* coef_dev, long long coef_len, const float* lut, float* out, int res_h, int res_w,
+                  void* stream);
+/* torchvision's make_grid(nrow, padding, pad_value) and save_image's quantisation in one launch (P/generate_images.py:181-235,
+ * P/evaluate_transvae.py:227-249): img fp32 [B, 3, H, W] with element strides (sn, sc, sh, sw), read in place -> out uint8
+ * [Hg, Wg, 3].  xmaps = min(nrow, B), ymaps = ceil(B / xmaps), Hg = (H + padding) ymaps + padding, Wg = (W + padding) xmaps + padding,
+ * image k at ((k / xmaps)(H + padding) + padding, (k % xmaps)(W + padding) + padding), everything else pad_value; B == 1 gives the
+ * image with no border (Hg = H, Wg = W).  Every value, pad_value included: x * 255, then + 0.5, each rounded to fp32 on its own,
+ * clamp to [0, 255], truncate; NaN gives 0.  TV_IMAGE_SIGMOID applies a sigmoid to the pixels first (P/generate_images.py:106,139,163). */
+#define TV_IMAGE_NONE 0
+#define TV_IMAGE_SIGMOID 1
+int tv_image_grid_u8(const float* img, long long sn, long long sc, long long sh, long long sw, void* out, int B, int H, int W, int nrow,
+                     int padding, float pad_value, int transform, void* stream);
 
 #ifdef __cplusplus
 }
