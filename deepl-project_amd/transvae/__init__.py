@@ -16,10 +16,14 @@ PSNR / SSIM / MSE from `reconstruction_metrics` (transvae/metrics.py), LPIPS fro
 with a `FrechetDistance`, computed on the device.  The image pipeline (transvae/image_io.py, csrc/image.hip): `ImagePrep` is the
 scripts' `Resize -> CenterCrop -> ToTensor` for a ragged uint8 batch (`collate_uint8` / `UInt8Batch`) in one launch, bit-equal to
 PIL; `to_uint8_grid` / `save_image` stand in for torchvision's `make_grid` / `save_image`; transvae/generate.py holds the three
-modes of P/generate_images.py.
+modes of P/generate_images.py.  Latent extraction and latent-space analysis (transvae/latents.py, csrc/latent.hip):
+`extract_latents` writes the encoder's latents and their per-channel statistics (`LatentStats`, streaming fp64 moments) for a
+downstream generator; `latent_points`, `latent_density_metrics` and `latent_space_metrics` compute the density CV / normalised
+entropy / Gini table from a log-domain Gaussian kernel density estimate.
 """
 from .evaluate import evaluate
 from .generate import interpolate_latents, random_samples, reconstruct
+from .latents import LatentStats, extract_latents, latent_density_metrics, latent_points, latent_space_metrics
 from .image_io import ImagePrep, UInt8Batch, collate_uint8, save_image, to_uint8_grid
 from .losses.lpips import PerceptualLoss
 from .losses.vae_loss import DiscriminatorLoss, TransVAELoss
@@ -32,4 +36,5 @@ from .models.transvae import TransVAE, create_transvae
 __version__ = "0.2.0"
 __all__ = ["TransVAE", "create_transvae", "TransVAELoss", "reconstruction_metrics", "evaluate", "PerceptualLoss", "DiscriminatorLoss",
            "PatchDiscriminator", "InceptionFeatures", "FrechetDistance", "VFLoss", "DinoV2Features", "ImagePrep", "UInt8Batch",
-           "collate_uint8", "to_uint8_grid", "save_image", "random_samples", "interpolate_latents", "reconstruct"]
+           "collate_uint8", "to_uint8_grid", "save_image", "random_samples", "interpolate_latents", "reconstruct", "LatentStats",
+           "extract_latents", "latent_points", "latent_density_metrics", "latent_space_metrics"]

@@ -124,6 +124,8 @@ SIGNATURES = {
     "tv_bilinear_nchw_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "tv_image_prep": (_I, [_P, _LL, _P, _P, _I, _P, _P, _LL, _P, _P, _I, _I, _P]),
     "tv_image_grid_u8": (_I, [_P, _LL, _LL, _LL, _LL, _P, _I, _I, _I, _I, _I, _F, _I, _P]),
+    "tv_latent_stats": (_I, [_P, _LL, _LL, _I, _I, _I, _P, _P, _P]),
+    "tv_kde_logdensity": (_I, [_P, _I, _P, _I, _I, _I, _I, _F, _I, _P, _P, _P]),
 }
 
 _lib = None

@@ -527,6 +527,25 @@ int tv_image_prep(const void* src, long long src_bytes, const tv_image_desc* des
 int tv_image_grid_u8(const float* img, long long sn, long long sc, long long sh, long long sw, void* out, int B, int H, int W, int nrow,
                      int padding, float pad_value, int transform, void* stream);
 
+/* Latent-space statistics (csrc/latent.hip) ---------------------------------------------------------------------------------------
+ * tv_latent_stats: streaming first and second moments of latents x [B, D, P] fp32 (positions contiguous; sn, sc = element strides of
+ * the batch and channel axes, so a channel slice of a wider tensor is read in place), 1 <= D <= 64.  A sample is one (image,
+ * position) pair.  state: 1 + D + D * D doubles, zero-initialised by the caller: {count, mean[D], M2[D * D]}, M2 the centred scatter
+ * sum (x - mean)(x - mean)^T.  fp64 throughout: the batch mean per channel in a fixed order, the batch scatter about that mean, then
+ * Chan's update.  scratch: 192 + min(256, ceil(B * P / 512)) * D * D doubles.  No atomics: the same sequence of calls gives the same
+ * bits, and M2 is bit-symmetric; different cuts of one data set into calls agree to fp64 rounding, not bit for bit. */
+int tv_latent_stats(const float* x, long long sn, long long sc, int B, int D, int P, double* state, double* scratch, void* stream);
+/* Gaussian kernel density estimate in the log domain: out[i] = log sum_j exp(-inv_2h2 * |q_i - x_j|^2), i < M, j < N, fp32 in and
+ * out; x [N, d] with row stride ldx, q [M, d] with row stride ldq, 1 <= d <= 64, N <= 2^30, inv_2h2 > 0 (= 1 / (2 h^2)).  The caller
+ * adds the normaliser -log(N) - d/2 log(2 pi h^2) if it wants a density.  exclude_self != 0: q is x (M == N, N >= 2) and the term
+ * j == i is dropped by index; duplicates of a point still count.  Squared distances are direct differences (an fmaf chain over k in
+ * order), never the Gram form; a running reference (the nearest point so far) keeps every exponent <= 0, so a point far from all
+ * others gets a finite value.  scratch: 128 * M doubles when M < 2048 (the data range is then cut into up to 64 slices whose
+ * {reference, sum} pairs a second launch merges in order), unused otherwise (may be NULL).  The geometry is a function of (N, M, d)
+ * alone; no atomics; bit-reproducible.  Rounding contract: DESIGN.md section 3.1 row T. */
+int tv_kde_logdensity(const float* x, int N, const float* q, int M, int d, int ldx, int ldq, float inv_2h2, int exclude_self, float* out,
+                      double* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
