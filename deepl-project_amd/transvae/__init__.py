@@ -19,7 +19,10 @@ PIL; `to_uint8_grid` / `save_image` stand in for torchvision's `make_grid` / `sa
 modes of P/generate_images.py.  Latent extraction and latent-space analysis (transvae/latents.py, csrc/latent.hip):
 `extract_latents` writes the encoder's latents and their per-channel statistics (`LatentStats`, streaming fp64 moments) for a
 downstream generator; `latent_points`, `latent_density_metrics` and `latent_space_metrics` compute the density CV / normalised
-entropy / Gini table from a log-domain Gaussian kernel density estimate.
+entropy / Gini table from a log-domain Gaussian kernel density estimate.  Linear probing of latents (transvae/probe.py,
+csrc/probe.hip): `probe_rows` builds the classifier's bf16 operand from stored latents, `softmax_xent` is the cross-entropy with
+its gradient and top-1 / top-5 counts in one pass, `LinearProbe` one linear layer; `fit_linear_probe` trains it on
+`extract_latents` shards with `FusedAdamW` and `linear_probe_accuracy` runs the extraction first.
 """
 from .evaluate import evaluate
 from .generate import interpolate_latents, random_samples, reconstruct
@@ -29,6 +32,7 @@ from .losses.lpips import PerceptualLoss
 from .losses.vae_loss import DiscriminatorLoss, TransVAELoss
 from .losses.vf import DinoV2Features, VFLoss
 from .metrics import reconstruction_metrics
+from .probe import LinearProbe, fit_linear_probe, linear_probe_accuracy, probe_rows, softmax_xent
 from .metrics_fid import FrechetDistance, InceptionFeatures
 from .models.discriminator import PatchDiscriminator
 from .models.transvae import TransVAE, create_transvae
@@ -37,4 +41,5 @@ __version__ = "0.2.0"
 __all__ = ["TransVAE", "create_transvae", "TransVAELoss", "reconstruction_metrics", "evaluate", "PerceptualLoss", "DiscriminatorLoss",
            "PatchDiscriminator", "InceptionFeatures", "FrechetDistance", "VFLoss", "DinoV2Features", "ImagePrep", "UInt8Batch",
            "collate_uint8", "to_uint8_grid", "save_image", "random_samples", "interpolate_latents", "reconstruct", "LatentStats",
-           "extract_latents", "latent_points", "latent_density_metrics", "latent_space_metrics"]
+           "extract_latents", "latent_points", "latent_density_metrics", "latent_space_metrics", "probe_rows", "softmax_xent", "LinearProbe",
+           "fit_linear_probe", "linear_probe_accuracy"]

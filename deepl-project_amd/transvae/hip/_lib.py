@@ -126,6 +126,9 @@ SIGNATURES = {
     "tv_image_grid_u8": (_I, [_P, _LL, _LL, _LL, _LL, _P, _I, _I, _I, _I, _I, _F, _I, _P]),
     "tv_latent_stats": (_I, [_P, _LL, _LL, _I, _I, _I, _P, _P, _P]),
     "tv_kde_logdensity": (_I, [_P, _I, _P, _I, _I, _I, _I, _F, _I, _P, _P, _P]),
+    "tv_probe_rows": (_I, [_P, _LL, _LL, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "tv_softmax_xent_partial_count": (_LL, [_I]),
+    "tv_softmax_xent": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P]),
 }
 
 _lib = None

@@ -546,6 +546,28 @@ int tv_latent_stats(const float* x, long long sn, long long sc, int B, int D, in
 int tv_kde_logdensity(const float* x, int N, const float* q, int M, int d, int ldx, int ldq, float inv_2h2, int exclude_self, float* out,
                       double* scratch, void* stream);
 
+/* Linear probing of latents (csrc/probe.hip) ---------------------------------------------------------------------------------------
+ * tv_probe_rows: fp32 latents x [B, D, h, w] (rows of w contiguous floats, planes of h * w; sn, sc = element strides of the batch
+ * and channel axes, so the mu half of a moments tensor is read in place) -> bf16 rows [B, ld], the classifier's operand.  Every
+ * channel is average-pooled to a gh x gw grid (gh | h, gw | w; gh = h, gw = w: no pooling) -- the fp32 sum of the window in scan
+ * order times 1 / window --, standardised (v - mean[c]) * rstd[c] in fp32 and rounded once.  Column (py * gw + px) * D + c;
+ * ld % 32 == 0 (tv_igemm_nt's c_in rule), ld >= gh * gw * D, the columns past gh * gw * D are exactly 0.  rows 16-byte aligned.
+ * Rounding contract: DESIGN.md section 3.1 row C. */
+int tv_probe_rows(const float* x, long long sn, long long sc, const float* mean, const float* rstd, void* rows, int B, int D, int h,
+                  int w, int gh, int gw, int ld, void* stream);
+/* Softmax cross-entropy of bf16 logits [B, ld] (columns 0 .. n_classes - 1 valid, ld % 8 == 0) against int64 labels [B] with label
+ * smoothing: per row lse - (1 - eps) x_y - (eps / n) sum_j x_j, and the rank of the label's logit = the columns with a strictly
+ * greater logit plus the columns with an equal logit and a lower index.  dlogits (bf16 [B, ld]; NULL: evaluation) receives
+ * grad_scale * (softmax - target), target = (1 - eps) [j == y] + eps / n, computed in fp32 and rounded once, pad columns exactly 0.
+ * state: 4 doubles {loss sum, rows counted, top-1 hits (rank 0), top-5 hits (rank < 5)} that the call ADDS to (zero it to start; read it
+ * with one synchronisation when the metrics are wanted).  A row whose label is outside [0, n_classes) gets a zero gradient row and is not counted.
+ * partials: tv_softmax_xent_partial_count(B) doubles of scratch.  One wave per row, the row in registers up to n_classes = 4096,
+ * three sweeps over memory above; block partials are added in block order in fp64: no atomics, bit-reproducible.
+ * Rounding contract: DESIGN.md section 3.1 row C. */
+long long tv_softmax_xent_partial_count(int B);
+int tv_softmax_xent(const void* logits, const long long* labels, void* dlogits, double* state, double* partials, int B, int n_classes,
+                    int ld, float label_smoothing, float grad_scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
