@@ -68,8 +68,9 @@ __global__ __launch_bounds__(256) void fid_prep_kernel(const float* __restrict__
                 const float* p = src + (size_t)c * H * W;
                 float v00 = p[(size_t)y0 * W + x0], v01 = p[(size_t)y0 * W + x1], v10 = p[(size_t)y1 * W + x0], v11 = p[(size_t)y1 * W + x1];
                 if (clip) {
-                    v00 = fminf(fmaxf(v00, 0.f), 1.f); v01 = fminf(fmaxf(v01, 0.f), 1.f);
-                    v10 = fminf(fmaxf(v10, 0.f), 1.f); v11 = fminf(fmaxf(v11, 0.f), 1.f);
+                    // torch.clamp: a NaN passes through into every output pixel that reads it (fminf / fmaxf drop it)
+                    v00 = v00 < 0.f ? 0.f : (v00 > 1.f ? 1.f : v00); v01 = v01 < 0.f ? 0.f : (v01 > 1.f ? 1.f : v01);
+                    v10 = v10 < 0.f ? 0.f : (v10 > 1.f ? 1.f : v10); v11 = v11 < 0.f ? 0.f : (v11 > 1.f ? 1.f : v11);
                 }
                 const float top = fmaf(lx, v01 - v00, v00), bot = fmaf(lx, v11 - v10, v10);
                 f = fmaf(2.f, fmaf(ly, bot - top, top), -1.f);

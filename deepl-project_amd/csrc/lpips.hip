@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void maxpool2x2_bwd_kernel(const bf16* __restr
 __device__ __forceinline__ float prep_value(float v, int flags, float shift, float scale) {
     if (flags & PREP_SIGMOID) v = tv_sigmoid(v);
     if (flags & PREP_MAP) v = fmaf(2.f, v, -1.f);
-    if (flags & PREP_CLAMP) v = fminf(fmaxf(v, -1.f), 1.f);
+    if (flags & PREP_CLAMP) v = v < -1.f ? -1.f : (v > 1.f ? 1.f : v);   // torch.clamp: a NaN passes through (fminf / fmaxf drop it)
     return (v - shift) / scale;
 }
 

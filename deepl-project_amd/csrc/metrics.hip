@@ -33,7 +33,9 @@ template <int K> struct MetTile {
 };
 
 __device__ __forceinline__ float met_transform(float v, int xform, bool is_recon) {
-    if (xform == TV_METRIC_CLIP) return fminf(fmaxf(v, 0.f), 1.f);
+    // np.clip / torch.clamp: a NaN is neither below 0 nor above 1 and passes through, so a diverged reconstruction reports
+    // NaN (fminf / fmaxf return the other operand and would report the metrics of a black pixel)
+    if (xform == TV_METRIC_CLIP) return v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
     if (xform == TV_METRIC_SIGMOID && is_recon) return 1.f / (1.f + expf(-v));
     return v;
 }

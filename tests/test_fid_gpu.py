@@ -100,6 +100,23 @@ def test_fid_prep(B, Hh, W):
     assert torch.equal(c1, c2)
 
 
+def test_fid_prep_clip_passes_a_nan_on():
+    """torch.clamp propagates a NaN: under clip a NaN pixel is NaN in exactly the patch columns where the restatement
+    (`clamp(0, 1)`, then the same resize) has NaN, and every other element keeps its bits"""
+    from transvae import metrics_fid as MF
+    g = torch.Generator().manual_seed(41)
+    z = torch.rand(2, 3, 64, 96, generator=g) * 1.5 - 0.25
+    clean = MF.fid_prep(z[:1].to(DEV), z[1:].to(DEV), clip=True).cpu()
+    bad = z.clone()
+    bad[1, 1, 30, 50] = float("nan")
+    got = MF.fid_prep(bad[:1].to(DEV), bad[1:].to(DEV), clip=True).cpu()
+    want = torch.zeros(got.shape, dtype=torch.bool)
+    want[..., :27] = H.fid_prep64(bad.clamp(0, 1)).isnan()
+    assert 0 < int(want.sum()) and not bool(want[0].any())
+    assert torch.equal(got.isnan(), want)
+    assert torch.equal(got.view(torch.int16)[~want], clean.view(torch.int16)[~want])
+
+
 def test_global_avgpool():
     from transvae import metrics_fid as MF
     x = _acts((5, 8, 8, 2048), 3)

@@ -229,6 +229,38 @@ def test_prep_and_its_adjoint(net, flags):
     assert rel < 1e-5                                          # fp32 sums of 9 exact bf16 terms, fp32 scalings
 
 
+@pytest.mark.parametrize("sigmoid", [False, True])
+def test_prep_clamp_passes_a_nan_on(net, sigmoid):
+    """torch.clamp propagates a NaN: with the clamp flag a NaN pixel of the reconstruction is NaN in exactly the patch columns
+    that hold it in the torch restatement (sigmoid, 2x - 1, clamp, scale, unfold), and every other element keeps its bits"""
+    from transvae.hip import _lib as L, ops
+    from transvae.losses import lpips as LP
+    g = torch.Generator().manual_seed(29)
+    B, H, W = 2, 16, 32
+    a = torch.randn(B, 3, H, W, generator=g) * 2.0
+    b = torch.rand(B, 3, H, W, generator=g) * 1.4 - 0.2
+    fa, fb = LP._prep_flags(True, sigmoid, True), LP._prep_flags(True, False, True)
+
+    def run(a):
+        cols = torch.empty(2 * B, H, W, 32, dtype=BF, device=DEV)
+        ad, bd = a.to(DEV), b.to(DEV)
+        L.check(L.load().tv_lpips_prep(ops._p(ad), ops._p(bd), ops._p(cols), B, B, H, W, fa, fb, ops._p(net.shift_scale), ops._stream()), "prep")
+        return cols.cpu()
+
+    clean = run(a)
+    bad = a.clone()
+    bad[1, 2, 7, 13] = float("nan")
+    bad[0, 0, 0, 0] = float("nan")                         # a corner: its patches are partly padding
+    got = run(bad)
+    v = torch.sigmoid(bad.to(F64)) if sigmoid else bad.to(F64)
+    v = ((2 * v - 1).clamp(-1, 1) - torch.tensor(R.SHIFT, dtype=F64).view(1, 3, 1, 1)) / torch.tensor(R.SCALE, dtype=F64).view(1, 3, 1, 1)
+    want = torch.zeros(2 * B, H, W, 32, dtype=torch.bool)
+    want[:B, ..., :27] = F.unfold(v, 3, padding=1).view(B, 3, 9, H, W).permute(0, 3, 4, 2, 1).reshape(B, H, W, 27).isnan()
+    assert int(want.sum()) == 9 + 4
+    assert torch.equal(got.isnan(), want)
+    assert torch.equal(got.view(torch.int16)[~want], clean.view(torch.int16)[~want])
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # whole loss
 # ---------------------------------------------------------------------------------------------------------------------
