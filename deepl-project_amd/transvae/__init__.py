@@ -22,8 +22,13 @@ downstream generator; `latent_points`, `latent_density_metrics` and `latent_spac
 entropy / Gini table from a log-domain Gaussian kernel density estimate.  Linear probing of latents (transvae/probe.py,
 csrc/probe.hip): `probe_rows` builds the classifier's bf16 operand from stored latents, `softmax_xent` is the cross-entropy with
 its gradient and top-1 / top-5 counts in one pass, `LinearProbe` one linear layer; `fit_linear_probe` trains it on
-`extract_latents` shards with `FusedAdamW` and `linear_probe_accuracy` runs the extraction first.
+`extract_latents` shards with `FusedAdamW` and `linear_probe_accuracy` runs the extraction first.  The latent diffusion transformer
+(transvae/dit.py, csrc/dit.hip): `DiT` / `create_dit` are adaLN-Zero DiT blocks on the stored latents (token GEMMs and attention on
+the existing kernels, the conditioning arithmetic and the flow-matching edge in csrc/dit.hip); `flow_matching_loss` is one training
+step's loss and backward, `fit_dit` trains on `extract_latents` shards with `FusedAdamW`, `sample_latents` / `sample_images`
+integrate the velocity field with Euler steps and classifier-free guidance and decode through the autoencoder.
 """
+from .dit import DiT, create_dit, fit_dit, flow_matching_loss, sample_images, sample_latents
 from .evaluate import evaluate
 from .generate import interpolate_latents, random_samples, reconstruct
 from .latents import LatentStats, extract_latents, latent_density_metrics, latent_points, latent_space_metrics
@@ -42,4 +47,4 @@ __all__ = ["TransVAE", "create_transvae", "TransVAELoss", "reconstruction_metric
            "PatchDiscriminator", "InceptionFeatures", "FrechetDistance", "VFLoss", "DinoV2Features", "ImagePrep", "UInt8Batch",
            "collate_uint8", "to_uint8_grid", "save_image", "random_samples", "interpolate_latents", "reconstruct", "LatentStats",
            "extract_latents", "latent_points", "latent_density_metrics", "latent_space_metrics", "probe_rows", "softmax_xent", "LinearProbe",
-           "fit_linear_probe", "linear_probe_accuracy"]
+           "fit_linear_probe", "linear_probe_accuracy", "DiT", "create_dit", "flow_matching_loss", "sample_latents", "sample_images", "fit_dit"]

@@ -129,6 +129,16 @@ SIGNATURES = {
     "tv_probe_rows": (_I, [_P, _LL, _LL, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "tv_softmax_xent_partial_count": (_LL, [_I]),
     "tv_softmax_xent": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P]),
+    "tv_adaln_fwd": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _I, _F, _P]),
+    "tv_adaln_bwd_partial_count": (_LL, [_I, _I, _I]),
+    "tv_adaln_bwd": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
+    "tv_gate_residual_fwd": (_I, [_P, _P, _P, _I, _I, _P, _I, _I, _I, _P]),
+    "tv_gate_residual_bwd_partial_count": (_LL, [_I, _I, _I]),
+    "tv_gate_residual_bwd": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
+    "tv_flow_rows": (_I, [_P, _LL, _LL, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "tv_flow_loss_partial_count": (_LL, [_I, _I, _I, _I, _I, _I]),
+    "tv_flow_loss": (_I, [_P, _P, _LL, _LL, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
+    "tv_flow_euler": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P]),
 }
 
 _lib = None

@@ -568,6 +568,44 @@ long long tv_softmax_xent_partial_count(int B);
 int tv_softmax_xent(const void* logits, const long long* labels, void* dlogits, double* state, double* partials, int B, int n_classes,
                     int ld, float label_smoothing, float grad_scale, void* stream);
 
+/* Latent DiT: adaLN-Zero conditioning and the flow-matching edge (csrc/dit.hip) --------------------------------------------------------
+ * Token matrices are bf16 [B N, C] (row r belongs to sample r / N; C % 8 == 0; 16-byte aligned).  mod is the fp32 [B, ld] modulation
+ * matrix of the block; shift / scale / gate are C columns of it starting at the given offsets (offset + C <= ld).  dmod has mod's
+ * shape; the backward calls WRITE their column ranges of it (no accumulation, no atomics: per lane the rows in order, per block the
+ * waves in order, then the row slabs of a sample in order -- the same bits on every run).  Rounding contract: DESIGN.md section 3.1
+ * row E; protocol: section 3.4.
+ * tv_adaln_fwd: y = bf16(fma(xhat, 1 + scale, shift)), xhat = (x - mean) rstd with two-pass fp32 statistics of the row (the scheme
+ * of tv_rownorm_fwd mode 2), affine-free.  C <= 1536.
+ * tv_adaln_bwd: statistics recomputed; g = dy (1 + scale); dx = bf16(rstd (g - mean(g) - xhat mean(g xhat)) + dres) (dres bf16 or
+ * NULL, joined in fp32); dmod[b, shift_off + c] = sum_n dy, dmod[b, scale_off + c] = sum_n dy xhat.  The two ranges must not overlap.
+ * partials: tv_adaln_bwd_partial_count(B, N, C) floats of scratch. */
+int tv_adaln_fwd(const void* x, const float* mod, int shift_off, int scale_off, int ld, void* y, int B, int N, int C, float eps, void* stream);
+long long tv_adaln_bwd_partial_count(int B, int N, int C);
+int tv_adaln_bwd(const void* x, const float* mod, int shift_off, int scale_off, int ld, const void* dy, const void* dres, void* dx, float* dmod,
+                 float* partials, int B, int N, int C, float eps, void* stream);
+/* tv_gate_residual_fwd: out = bf16(fma(gate, y, x)).  tv_gate_residual_bwd: dy = bf16(gate dout), dmod[b, gate_off + c] = sum_n dout y;
+ * the gradient of x is dout itself.  C <= 2048.  partials: tv_gate_residual_bwd_partial_count(B, N, C) floats of scratch. */
+int tv_gate_residual_fwd(const void* x, const void* y, const float* mod, int gate_off, int ld, void* out, int B, int N, int C, void* stream);
+long long tv_gate_residual_bwd_partial_count(int B, int N, int C);
+int tv_gate_residual_bwd(const void* dout, const void* y, const float* mod, int gate_off, int ld, void* dy, float* dmod, float* partials, int B,
+                         int N, int C, void* stream);
+/* Flow matching on fp32 latents lat [B, D, h, w] (sn, sc = element strides of the batch and channel axes, as tv_probe_rows takes
+ * them).  With x = (lat - mean[c]) * rstd[c] (two fp32 roundings) and patch size p (p | h, p | w), token (ty, tx) of sample b is row
+ * b N + ty (w / p) + tx, N = (h / p)(w / p), and element (py, px, c) of its patch is column (py p + px) D + c; ld % 32 == 0,
+ * ld >= p p D, the columns past p p D are exactly 0.  noise is dense fp32 [B, D, h, w], t fp32 [B].
+ * tv_flow_rows: rows = bf16(fma(t, x, (1 - t) e)); noise NULL: rows = bf16(x), the plain patchify (t is not read).
+ * tv_flow_loss: d = pred - (x - e) over the real columns; out[0] = sum d^2, out[1] = out[0] / (B N p p D), fp64 (per thread in
+ * element order, per wave a butterfly, per block its four waves in order, then the blocks in order); dpred (bf16 or NULL) =
+ * bf16(fp32(2 grad_scale / count) * d), pad columns exactly 0.  partials: tv_flow_loss_partial_count(...) doubles of scratch.
+ * tv_flow_euler: x (dense fp32 [B, D, h, w]) += dt v with v read from bf16 rows [B N, ld]; guided != 0: v has 2 B N rows, the first
+ * B N conditional (v_c), the rest unconditional (v_u), and v = fma(cfg_scale, v_c - v_u, v_u); every sum is one fp32 operation. */
+int tv_flow_rows(const float* lat, long long sn, long long sc, const float* mean, const float* rstd, const float* noise, const float* t, void* rows,
+                 int B, int D, int h, int w, int patch, int ld, void* stream);
+long long tv_flow_loss_partial_count(int B, int D, int h, int w, int patch, int ld);
+int tv_flow_loss(const void* pred, const float* lat, long long sn, long long sc, const float* mean, const float* rstd, const float* noise,
+                 void* dpred, double* out, double* partials, int B, int D, int h, int w, int patch, int ld, float grad_scale, void* stream);
+int tv_flow_euler(float* x, const void* v, int B, int D, int h, int w, int patch, int ld, float dt, float cfg_scale, int guided, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
