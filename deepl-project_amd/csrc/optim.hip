@@ -5,6 +5,8 @@
 //                      the update, a non-finite step is skipped on the device, and the bf16 copy of each weight (the
 //                      forward operand of tv_igemm_nt) is written in the same pass
 //   tv_pack_weight_multi   all transposed (data-gradient) operands refreshed from those bf16 copies in one launch
+//   tv_opt_ema         exponential moving average of every weight in one launch: ema = fmaf(1 - decay, w - ema, ema), so
+//                      w == ema leaves the bits alone; skipped on the device with the optimizer step it follows
 //
 // Reference behaviour: torch.optim.AdamW(lr, betas, eps, weight_decay) -- R/train.py:681-687;
 // clip_grad_norm_(max_norm) -- R/train.py:610-612; skip on non-finite -- R/train_2.py:328-338.
@@ -13,7 +15,8 @@
 //     m   = m + (g - m) * (1 - beta1)
 //     v   = beta2 * v + (1 - beta2) * g * g
 //     p  -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
-// Algorithmic bytes per parameter element: norm 4 (read g) ; update 4 (g) + 3 * 8 (p, m, v read + write) + 2 (bf16 copy).
+// Algorithmic bytes per parameter element: norm 4 (read g) ; update 4 (g) + 3 * 8 (p, m, v read + write) + 2 (bf16 copy) ;
+// EMA 4 (w) + 8 (ema read + write).
 #include "common.h"
 
 namespace {
@@ -178,6 +181,34 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_cast_kernel(const OptTensor* 
     for (long long i = start + threadIdx.x; i < end; i += OPT_THREADS) t.shadow[i] = (bf16)t.param[i];
 }
 
+// table rows: param = the EMA tensor, grad = the source weight, the other pointers unused
+__global__ __launch_bounds__(OPT_THREADS) void opt_ema_kernel(const OptTensor* __restrict__ tab, const int2* __restrict__ chunks,
+                                                              const float* __restrict__ ctrl, float a) {
+    if (ctrl && ctrl[3] != 0.f) return;   // the optimizer skipped this step (uniform over the grid)
+    const int2 c = chunks[blockIdx.x];
+    const OptTensor t = tab[c.x];
+    const long long start = (long long)c.y * OPT_CHUNK;
+    const long long end = min(t.numel, start + OPT_CHUNK);
+    long long tail = start;
+    if (((((uintptr_t)t.param) | ((uintptr_t)t.grad)) & 15) == 0) {
+        const long long n4 = (end - start) >> 2;
+        f32x4* e4 = (f32x4*)(t.param + start);
+        const f32x4* w4 = (const f32x4*)(t.grad + start);
+        for (long long i = threadIdx.x; i < n4; i += OPT_THREADS) {
+            f32x4 e = e4[i];
+            const f32x4 w = w4[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) e[j] = fmaf(a, w[j] - e[j], e[j]);
+            e4[i] = e;
+        }
+        tail = start + (n4 << 2);
+    }
+    for (long long i = tail + threadIdx.x; i < end; i += OPT_THREADS) {
+        const float e = t.param[i];
+        t.param[i] = fmaf(a, t.grad[i] - e, e);
+    }
+}
+
 // ---- all transposed operands in one launch: bf16 [O][T][I] -> bf16 [I][T'][O] -----------------------------------------
 struct PackForm {   // == struct tv_pack_form
     const bf16* src;
@@ -248,6 +279,16 @@ extern "C" int tv_opt_cast_shadows(const tv_opt_tensor* table_dev, const int* ch
     hipLaunchKernelGGL(opt_cast_kernel, dim3(n_chunks), dim3(OPT_THREADS), 0, (hipStream_t)stream, (const OptTensor*)table_dev,
                        (const int2*)chunks_dev);
     TV_CHECK_LAUNCH("tv_opt_cast_shadows");
+    return TV_OK;
+}
+
+extern "C" int tv_opt_ema(const tv_opt_tensor* table_dev, const int* chunks_dev, int n_chunks, const float* ctrl, float one_minus_decay,
+                          void* stream) {
+    TV_CHECK_ARG(table_dev && chunks_dev && n_chunks > 0, "tv_opt_ema: bad arguments");
+    TV_CHECK_ARG(one_minus_decay >= 0.f && one_minus_decay <= 1.f, "tv_opt_ema: one_minus_decay=%g must be in [0, 1]", (double)one_minus_decay);
+    hipLaunchKernelGGL(opt_ema_kernel, dim3(n_chunks), dim3(OPT_THREADS), 0, (hipStream_t)stream, (const OptTensor*)table_dev,
+                       (const int2*)chunks_dev, ctrl, one_minus_decay);
+    TV_CHECK_LAUNCH("tv_opt_ema");
     return TV_OK;
 }
 

@@ -26,10 +26,15 @@ its gradient and top-1 / top-5 counts in one pass, `LinearProbe` one linear laye
 (transvae/dit.py, csrc/dit.hip): `DiT` / `create_dit` are adaLN-Zero DiT blocks on the stored latents (token GEMMs and attention on
 the existing kernels, the conditioning arithmetic and the flow-matching edge in csrc/dit.hip); `flow_matching_loss` is one training
 step's loss and backward, `fit_dit` trains on `extract_latents` shards with `FusedAdamW`, `sample_latents` / `sample_images`
-integrate the velocity field with Euler steps and classifier-free guidance and decode through the autoencoder.
+integrate the velocity field with Euler steps and classifier-free guidance and decode through the autoencoder.  Generator evaluation
+(transvae/evaluate_dit.py, transvae/metrics_gen.py, csrc/genmetrics.hip): `evaluate_dit` samples, extracts Inception features and
+returns gFID, Inception Score (`InceptionScore`) and the k-NN precision / recall (`knn_radius`, `manifold_hits`,
+`precision_recall`) against a `reference_statistics` dict; `ParamEMA` (transvae/optim.py) is the weight average they are measured on,
+kept by `fit_dit(..., ema_decay=...)`.
 """
 from .dit import DiT, create_dit, fit_dit, flow_matching_loss, sample_images, sample_latents
 from .evaluate import evaluate
+from .evaluate_dit import evaluate_dit
 from .generate import interpolate_latents, random_samples, reconstruct
 from .latents import LatentStats, extract_latents, latent_density_metrics, latent_points, latent_space_metrics
 from .image_io import ImagePrep, UInt8Batch, collate_uint8, save_image, to_uint8_grid
@@ -39,6 +44,8 @@ from .losses.vf import DinoV2Features, VFLoss
 from .metrics import reconstruction_metrics
 from .probe import LinearProbe, fit_linear_probe, linear_probe_accuracy, probe_rows, softmax_xent
 from .metrics_fid import FrechetDistance, InceptionFeatures
+from .metrics_gen import InceptionScore, knn_radius, manifold_hits, precision_recall, reference_statistics
+from .optim import ParamEMA
 from .models.discriminator import PatchDiscriminator
 from .models.transvae import TransVAE, create_transvae
 
@@ -47,4 +54,5 @@ __all__ = ["TransVAE", "create_transvae", "TransVAELoss", "reconstruction_metric
            "PatchDiscriminator", "InceptionFeatures", "FrechetDistance", "VFLoss", "DinoV2Features", "ImagePrep", "UInt8Batch",
            "collate_uint8", "to_uint8_grid", "save_image", "random_samples", "interpolate_latents", "reconstruct", "LatentStats",
            "extract_latents", "latent_points", "latent_density_metrics", "latent_space_metrics", "probe_rows", "softmax_xent", "LinearProbe",
-           "fit_linear_probe", "linear_probe_accuracy", "DiT", "create_dit", "flow_matching_loss", "sample_latents", "sample_images", "fit_dit"]
+           "fit_linear_probe", "linear_probe_accuracy", "DiT", "create_dit", "flow_matching_loss", "sample_latents", "sample_images", "fit_dit",
+           "evaluate_dit", "InceptionScore", "knn_radius", "manifold_hits", "precision_recall", "reference_statistics", "ParamEMA"]

@@ -26,7 +26,7 @@ import torch.nn.functional as F
 from .hip import _lib as L
 from .hip import ops
 from .modules.attention import RoPE2D
-from .optim import FusedAdamW
+from .optim import FusedAdamW, ParamEMA
 from .probe import _Shards, _round_up, _stat_vectors
 
 LN_EPS = 1e-6
@@ -573,14 +573,18 @@ def sample_images(vae: nn.Module, dit: DiT, labels: torch.Tensor, *, steps: int,
 
 
 def fit_dit(train_dir, dit: DiT, *, epochs: int, batch_size: int, lr: float, weight_decay: float = 0.0, t_sampling: str = "lognorm",
-            use_flip: bool = True, seed: int = 0, log_every: int = 50, device="cuda") -> Dict:
+            use_flip: bool = True, seed: int = 0, log_every: int = 50, device="cuda", ema_decay: Optional[float] = None) -> Dict:
     """Train `dit` by flow matching on an `extract_latents` directory (or a `(latents, labels)` pair with `stats` as a third item).
 
     Shards stream one at a time in an order drawn per epoch from a host generator seeded with `seed + 1`, with a permutation inside
     each shard; with `use_flip` and `latents_flip` in the shard every sample is its mirrored latent with probability 1/2, drawn by
     the same generator.  t, the noise and the label dropout come from a device generator seeded with `seed`.  `FusedAdamW`,
     constant learning rate; the loss is read back once per `log_every` steps (one host synchronisation each).
+    With `ema_decay` a `ParamEMA` of the weights (equal to them at the start) is updated after every optimizer step and returned
+    under "ema"; with None nothing is kept and there is no such key.
     Returns {"loss" (mean of the last logging interval), "history" [{"step", "loss"}], "shard_orders", "steps", "optimizer"}."""
+    if ema_decay is not None and not 0.0 <= float(ema_decay) <= 1.0:
+        raise ValueError(f"fit_dit: ema_decay={ema_decay!r} must be in [0, 1] or None")
     if epochs < 1 or batch_size < 1 or not lr > 0 or log_every < 1:
         raise ValueError("fit_dit: epochs, batch_size, lr and log_every must be positive")
     device = torch.device(device)
@@ -599,6 +603,7 @@ def fit_dit(train_dir, dit: DiT, *, epochs: int, batch_size: int, lr: float, wei
         _stats_of(stats, dit.in_channels, device)
         dit.to(device).train()
         opt = FusedAdamW(dit.parameters(), lr=lr, weight_decay=weight_decay)
+        ema = ParamEMA(dit.parameters(), decay=float(ema_decay), optimizer=opt) if ema_decay is not None else None
         order_gen = torch.Generator().manual_seed(int(seed) + 1)
         dev_gen = torch.Generator(device=device).manual_seed(int(seed))
         acc = torch.zeros((), dtype=torch.float64, device=device)
@@ -622,6 +627,8 @@ def fit_dit(train_dir, dit: DiT, *, epochs: int, batch_size: int, lr: float, wei
                     opt.zero_grad(set_to_none=True)
                     acc += flow_matching_loss(dit, x, lab[idx], stats, generator=dev_gen, t_sampling=t_sampling, check_labels=False)
                     opt.step()
+                    if ema is not None:
+                        ema.update()
                     step += 1
                     pending += 1
                     if pending == log_every:
@@ -631,4 +638,7 @@ def fit_dit(train_dir, dit: DiT, *, epochs: int, batch_size: int, lr: float, wei
                 del lat, lab, flip
         if pending:
             history.append({"step": step, "loss": float(acc) / pending})
-    return {"loss": history[-1]["loss"], "history": history, "shard_orders": orders, "steps": step, "optimizer": opt}
+    out = {"loss": history[-1]["loss"], "history": history, "shard_orders": orders, "steps": step, "optimizer": opt}
+    if ema is not None:
+        out["ema"] = ema
+    return out

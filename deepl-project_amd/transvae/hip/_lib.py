@@ -91,6 +91,7 @@ SIGNATURES = {
     "tv_opt_adamw": (_I, [_P, _P, _I, _P, _F, _F, _F, _F, _F, _P]),
     "tv_opt_cast_shadows": (_I, [_P, _P, _I, _P]),
     "tv_pack_weight_multi": (_I, [_P, _I, _LL, _P]),
+    "tv_opt_ema": (_I, [_P, _P, _I, _P, _F, _P]),
     "tv_recon_metrics_partial_count": (_LL, [_I, _I, _I, _I, _I]),
     "tv_recon_metrics": (_I, [_P, _P] + [_LL] * 8 + [_I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "tv_maxpool2x2_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P]),
@@ -139,6 +140,9 @@ SIGNATURES = {
     "tv_flow_loss_partial_count": (_LL, [_I, _I, _I, _I, _I, _I]),
     "tv_flow_loss": (_I, [_P, _P, _LL, _LL, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "tv_flow_euler": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P]),
+    "tv_knn_radius": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "tv_manifold_hits": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P]),
+    "tv_softmax_stats": (_I, [_P, _I, _I, _I, _P, _P, _P]),
 }
 
 _lib = None

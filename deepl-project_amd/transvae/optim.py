@@ -19,9 +19,13 @@ from this optimizer's copies as long as the parameter has not been modified by a
 State layout is torch.optim.AdamW's (`state[p] = {step, exp_avg, exp_avg_sq}`), so `state_dict()` / `load_state_dict()`
 interchange with the reference's checkpoints (`optimizer_state_dict`, R/train.py:753-769).  The arithmetic is ATen's fused
 AdamW in fp32 (tests/test_train_gpu.py compares the two).  No CPU path: parameters must live on a HIP device.
+
+`ParamEMA` keeps an exponential moving average of the weights (the copy every published DiT FID is measured on) with one more
+multi-tensor launch per step, `tv_opt_ema`, over the same chunk tables.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Optional
 
@@ -193,3 +197,99 @@ class FusedAdamW(torch.optim.Optimizer):
                         t = torch.empty_strided(p.shape, p.stride(), dtype=torch.float32, device=p.device)
                         t.copy_(st[k])
                         st[k] = t
+
+
+class ParamEMA:
+    """Exponential moving average of `params`: fp32 copies, bit-equal to the parameters at construction.
+
+    `update()` is one `tv_opt_ema` launch: ema = fmaf(1 - decay, w - ema, ema), with 1 - decay taken in fp64 and rounded once.
+    Handed a `FusedAdamW` as `optimizer`, the launch does nothing when that optimizer's last step was skipped (non-finite
+    gradients), decided on the device.  `num_updates` counts the calls of `update()`."""
+
+    def __init__(self, params, decay: float = 0.9999, optimizer: Optional[FusedAdamW] = None):
+        ps = list(params)
+        if not 0.0 <= float(decay) <= 1.0:
+            raise ValueError(f"ParamEMA: decay={decay!r} must be in [0, 1]")
+        if not ps:
+            raise ValueError("ParamEMA: no parameters")
+        dev = ps[0].device
+        if dev.type != "cuda" or any(p.device != dev for p in ps):
+            raise RuntimeError("ParamEMA: all parameters must live on one HIP device (there is no CPU path)")
+        if any(p.dtype != torch.float32 or not _dense(p) for p in ps):
+            raise RuntimeError("ParamEMA: parameters must be dense fp32 tensors")
+        if optimizer is not None and not isinstance(optimizer, FusedAdamW):
+            raise TypeError("ParamEMA: optimizer must be a FusedAdamW (its device control block carries the skip flag)")
+        self.decay = float(decay)
+        self.num_updates = 0
+        self._dev = dev
+        self._params = ps
+        self._ctrl = optimizer._ctrl if optimizer is not None else None
+        self._chunk = L.load().tv_opt_chunk_elems()
+        with torch.cuda.device(dev), torch.no_grad():
+            self.shadow = [torch.empty_strided(p.shape, p.stride(), dtype=torch.float32, device=dev).copy_(p) for p in ps]
+            rows = []
+            for i, p in enumerate(ps):
+                n = (p.numel() + self._chunk - 1) // self._chunk
+                rows.append(torch.stack([torch.full((n,), i, dtype=torch.int32), torch.arange(n, dtype=torch.int32)], 1))
+            tab = torch.cat(rows, 0).contiguous()
+            self._chunks, self._n_chunks = tab.to(dev), tab.shape[0]
+        self._table = None        # (source pointers, device table, pinned source)
+
+    def _pointer_table(self):
+        key = tuple(p.data_ptr() for p in self._params)
+        if self._table is None or self._table[0] != key:
+            rows = [(e.data_ptr(), p.data_ptr(), 0, 0, 0, p.numel()) for e, p in zip(self.shadow, self._params)]
+            host = torch.tensor(rows, dtype=torch.int64).pin_memory()
+            self._table = (key, host.to(self._dev, non_blocking=True), host)
+        return self._table[1]
+
+    @torch.no_grad()
+    def update(self) -> None:
+        if any(p.stride() != e.stride() or p.dtype != torch.float32 or p.device != self._dev for p, e in zip(self._params, self.shadow)):
+            raise RuntimeError("ParamEMA: a parameter changed its device, dtype or memory layout")
+        with torch.cuda.device(self._dev):
+            tab = self._pointer_table()
+            L.check(L.load().tv_opt_ema(C.c_void_p(tab.data_ptr()), C.c_void_p(self._chunks.data_ptr()), self._n_chunks,
+                                        ops._p(self._ctrl), float(1.0 - self.decay), ops._stream()), "tv_opt_ema")
+        self.num_updates += 1
+
+    def _targets(self, params):
+        ps = list(params)
+        if len(ps) != len(self.shadow) or any(p.shape != e.shape for p, e in zip(ps, self.shadow)):
+            raise ValueError("ParamEMA: the parameters do not match the averaged ones in number or shape")
+        ops._need_gpu(*ps)
+        return ps
+
+    @torch.no_grad()
+    def copy_to(self, params) -> None:
+        """EMA values into `params` through `copy_` (the operand caches keyed on `_version` see the change)."""
+        for p, e in zip(self._targets(params), self.shadow):
+            p.copy_(e)
+
+    @contextlib.contextmanager
+    def applied(self, module: torch.nn.Module):
+        """Inside the block `module`'s parameters hold the EMA values; on exit they get their own bits back."""
+        ps = self._targets(module.parameters())
+        with torch.no_grad():
+            saved = [p.detach().clone(memory_format=torch.preserve_format) for p in ps]
+            for p, e in zip(ps, self.shadow):
+                p.copy_(e)
+        try:
+            yield module
+        finally:
+            with torch.no_grad():
+                for p, s0 in zip(ps, saved):
+                    p.copy_(s0)
+
+    def state_dict(self):
+        return {"decay": self.decay, "num_updates": self.num_updates, "shadow": [e.detach().clone() for e in self.shadow]}
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict) -> None:
+        sh = state_dict["shadow"]
+        if len(sh) != len(self.shadow) or any(tuple(a.shape) != tuple(e.shape) for a, e in zip(sh, self.shadow)):
+            raise ValueError("ParamEMA.load_state_dict: shadow does not match the averaged parameters in number or shape")
+        self.decay = float(state_dict["decay"])
+        self.num_updates = int(state_dict["num_updates"])
+        for a, e in zip(sh, self.shadow):
+            e.copy_(a)

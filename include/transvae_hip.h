@@ -271,6 +271,12 @@ int tv_opt_adamw(const tv_opt_tensor* table_dev, const int* chunks_dev, int n_ch
                  float lr, float beta1, float beta2, float eps, float weight_decay, void* stream);
 /* shadow_bf16 = (bf16) param for every tensor that has one (first fill) */
 int tv_opt_cast_shadows(const tv_opt_tensor* table_dev, const int* chunks_dev, int n_chunks, void* stream);
+/* Exponential moving average of the weights, one launch over a table whose rows use `param` for the EMA tensor (fp32, updated in
+ * place) and `grad` for the source weight (the other pointers are not read; NULL): ema = fmaf(a, w - ema, ema) with
+ * a = one_minus_decay, which the caller forms as 1 - decay in fp64 and rounds once.  w == ema leaves the bits unchanged.  ctrl: NULL,
+ * or the optimizer's control block: the launch is a no-op when ctrl[3] != 0 (that step was skipped).  Bound against fp64 with the
+ * same fp32 a: 2 u (|w| + |ema|).  Rounding contract: DESIGN.md section 3.1 row S. */
+int tv_opt_ema(const tv_opt_tensor* table_dev, const int* chunks_dev, int n_chunks, const float* ctrl, float one_minus_decay, void* stream);
 /* every transposed operand in one launch: src bf16 [O,T,I] -> dst_t bf16 [I,T',O] (T' reversed if flip);
  * tile_start = exclusive prefix sum of ceil(O/64)*ceil(I/64)*T over the forms */
 typedef struct tv_pack_form {
@@ -605,6 +611,32 @@ long long tv_flow_loss_partial_count(int B, int D, int h, int w, int patch, int 
 int tv_flow_loss(const void* pred, const float* lat, long long sn, long long sc, const float* mean, const float* rstd, const float* noise,
                  void* dpred, double* out, double* partials, int B, int D, int h, int w, int patch, int ld, float grad_scale, void* stream);
 int tv_flow_euler(float* x, const void* v, int B, int D, int h, int w, int patch, int ld, float dt, float cfg_scale, int guided, void* stream);
+
+
+/* Generation metrics (csrc/genmetrics.hip) -------------------------------------------------------------------------------------------
+ * Squared distance of the two pairwise kernels: D(a, b) = sum_c (a_c - b_c)^2 as ONE fp32 chain over c = 0 .. d - 1 in order, diff =
+ * a_c - b_c rounded once, acc = fmaf(diff, diff, acc); no partial chains (the accumulator stays in a register across the d-chunks),
+ * never the Gram form.  D(a, b) and D(b, a) are the same bits, and the bits of a pair depend on nothing but the two rows and d.
+ * Bound against fp64: (d + 2) u D, u = 2^-24.  1 <= d <= 8192, fp32 rows with strides ldx, ldq >= d; float4 loads when the bases are
+ * 16-byte aligned and the strides multiples of 4, scalar loads otherwise (the same bits).
+ * tv_knn_radius: for the queries i = i0 .. i0 + M - 1 of x [N, d], r2[i - i0] = the k-th smallest D(x_i, x_j) over j != i; self is
+ * excluded by index, duplicates of a point still count (= the (k + 1)-th smallest with self included).  1 <= k <= 8, N >= k + 1.
+ * tv_manifold_hits: hit[i] (int32) = 1 when some j < N has D(q_i, x_j) <= r2[j], compared on the fp32 values, else 0; i < M.
+ * scratch: when ceil(M / 64) < 512 the data range may be cut into up to 32 slices that a second launch merges in slice order:
+ * 256 * M floats (tv_knn_radius) or 32 * M ints (tv_manifold_hits); unused and may be NULL otherwise.  The geometry is a function of
+ * (N, M) alone, there are no atomics, and the output does not depend on the geometry: bit-reproducible, and the same for every cut of
+ * the query range into calls.  Every coordinate and every r2 must be finite: the k-lists are kept with fminf / fmaxf, which drop a NaN
+ * distance and repeat a list entry in its place, so non-finite rows corrupt the radii without a sign of it (evaluate_dit checks its
+ * features; a direct caller checks its own).  Rounding contract: DESIGN.md section 3.1 row S; protocol: section 3.5. */
+int tv_knn_radius(const float* x, int N, int d, int ldx, int i0, int M, int k, float* r2, float* scratch, void* stream);
+int tv_manifold_hits(const float* q, int M, int ldq, const float* x, int N, int ldx, const float* r2, int d, int* hit, int* scratch,
+                     void* stream);
+/* Softmax statistics of fp32 logits [B, K] (row stride ld >= K, 1 <= K <= 4096) for the Inception Score.  state: 2 + K doubles
+ * {rows, sum_rows sum_k p log p, sum_rows p_k} that the call ADDS to (zero it to start).  Everything after the load is fp64: z - max,
+ * exp, the row sum s in k order, log, p = e / s, log p = (z - max) - log s, the row's sum of p log p in k order.  The rows are added
+ * to the state one at a time in row order, so the state after n rows has the same bits however the rows were cut into calls.
+ * scratch: B * (K + 1) doubles.  Bound per state entry: 16 K 2^-53 relative to the sum of the absolute terms. */
+int tv_softmax_stats(const float* logits, int B, int K, int ld, double* state, double* scratch, void* stream);
 
 #ifdef __cplusplus
 }
