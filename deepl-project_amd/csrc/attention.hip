@@ -17,9 +17,6 @@
 // MFMA work for the whole backward instead of 2.5x) -- the trade is recorded in DESIGN.md.
 #include "common.h"
 
-#include <type_traits>
-#include <utility>
-
 namespace {
 
 // Diagnostic builds only (tools/probes/build_variant.sh ... -DTV_ATTN_ABL=<mask>; results are wrong, times are what is read):
@@ -44,36 +41,13 @@ __device__ __forceinline__ f32x16 mfma32b(bf16x8 a, bf16x8 b, f32x16 c) {   // s
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 #endif
 }
-// ds_read_b64_tr_b16 via inline asm: the builtin makes hipcc (ROCm 7.2) drain vmcnt(0) before each transposed read
-// while an LDS-DMA is in flight, serialising the K/V DMA with compute.  Callers wait with lds_wait_all() before use.
-__device__ __forceinline__ bf16x4 lds_tr16(const char* p) {
-    bf16x4 r;
-    const unsigned a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const char*)p;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(a) : "memory");
-    return r;
-}
-__device__ __forceinline__ void lds_wait_all() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
 #if TV_ATTN_ABL & 1
 __device__ __forceinline__ float fexp2(float x) { return x; }
 #else
 __device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }
 #endif
 
-// output rows (o, dq, dk, dv): non-temporal stores measured 0.7 % SLOWER in the bench (the consumer GEMM finds a small o / dqkv in the
-// Infinity Cache with the default policy; item 23) -- off, kept for A/B
-#ifndef TV_ATTN_NT_STORE
-#define TV_ATTN_NT_STORE 0
-#endif
-__device__ __forceinline__ void attn_store4(bf16* ptr, const bf16x4& v) {
-#if TV_ATTN_NT_STORE
-    __builtin_nontemporal_store(v, (bf16x4*)ptr);
-#else
-    *(bf16x4*)ptr = v;
-#endif
-}
+__device__ __forceinline__ void attn_store4(bf16* ptr, const bf16x4& v) { *(bf16x4*)ptr = v; }
 
 // ---- ring of K / V (Q / dO) stages -------------------------------------------------------------------------------
 // Round 3: the loops staged tile t+1 while computing tile t and opened every tile with `vmcnt(0)` + barrier: one tile of
@@ -88,31 +62,16 @@ __device__ __forceinline__ void attn_store4(bf16* ptr, const bf16x4& v) {
 #ifndef TV_ATTN_NS_DKV
 #define TV_ATTN_NS_DKV 2    // dk / dv: ring stages of TV_ATTN_DKV_QS x (Q 4 KiB + dO 4 KiB + 256 B); with two tiles per stage a ring of 2 measured best (3.17 -> 3.09-3.12 ms at N = 4096)
 #endif
-#ifndef TV_ATTN_SUM_MFMA
-#define TV_ATTN_SUM_MFMA 0  // forward: softmax row sums on the matrix pipe (an all-ones A operand) instead of 32 v_add_f32 per key block: measured 2.7 % SLOWER, off
-#endif
 #ifndef TV_ATTN_LAZY
 #define TV_ATTN_LAZY 8      // forward: rescale the running sums only when some row's maximum grew by more than this (log2 units); 0 = always
-#endif
-#ifndef TV_ATTN_DMA_LATE
-#define TV_ATTN_DMA_LATE 1    // next stage's DMA pieces after the first-phase MFMAs of a tile instead of right behind the barrier
-#endif
-#ifndef TV_ATTN_V_LATE
-#define TV_ATTN_V_LATE 0
 #endif
 #ifndef TV_ATTN_FWD64
 #define TV_ATTN_FWD64 2048  // forward: sequences of at least this many tokens take the 64-queries-per-wave kernel (0 = never): N = 4096 1.745 -> 1.693 ms, N = 1024 equal
 #endif
-#ifndef TV_ATTN_DELTA_MFMA
-#define TV_ATTN_DELTA_MFMA 1  // dq: -delta enters dP through one extra k-step (three bf16 pieces = fp32), not 16 v_add_f32 per tile
-#endif
-#ifndef TV_ATTN_DKV_ACCINIT
-#define TV_ATTN_DKV_ACCINIT 1 // dk / dv: -delta read from LDS straight into dP's initial accumulator
-#endif
 template <int N>
-__device__ __forceinline__ void vm_wait() {
+__device__ __forceinline__ void vm_wait() {   // wait_vmcnt, unless the ablation bit takes the waits out
 #if !(TV_ATTN_ABL & 16)
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+    wait_vmcnt<N>();
 #endif
 }
 __device__ __forceinline__ void block_sync() {
@@ -154,24 +113,10 @@ __device__ __forceinline__ float xhalf_sum(float x) {
 __device__ __forceinline__ int swz_row(int r) { return (r >> 1) & 7; }          // conflict-free ds_read_b128 rows
 __device__ __forceinline__ int swz_tr(int r) { return ((r >> 1) & 1) << 2; }    // conflict-free transposed reads
 
-// DMA `nrows` rows (multiple of 8) of a [*, ld] matrix starting at row g0 into a swizzled LDS tile.
-template <bool TR>
-__device__ __forceinline__ void stage_rows(char* lds, const bf16* base, int g0, int nvalid, size_t ld, int nrows,
-                                           int wave, int lane, const char* zeros) {
-    const int rsub = lane >> 3, slot = lane & 7;
-    for (int j = wave; j < nrows / 8; j += 4) {
-        const int row = j * 8 + rsub;
-        const int c = slot ^ (TR ? swz_tr(row) : swz_row(row));
-        const int gr = g0 + row;
-        const void* src = (gr < nvalid) ? (const void*)(base + (size_t)gr * ld + c * 8) : (const void*)(zeros + lane * 16);
-        __builtin_amdgcn_global_load_lds(TV_GLB(src), TV_LDS(lds + j * 1024), 16, 0, 0);
-    }
-}
-
-// The same staging through a buffer descriptor (tensors < 2 GiB per image): the per-lane offset of a piece inside the tile
+// DMA of rows of a [*, ld] matrix into a swizzled LDS tile through a buffer descriptor (tensors < 2 GiB per image): the per-lane offset of a piece inside the tile
 // (row, swizzled chunk) is fixed for the whole kernel, the tile's first row enters as the SCALAR offset and rows beyond
 // `nvalid` fall outside the descriptor's extent (the DMA writes zeros) -- no vector ALU work per tile.  The per-tile address
-// arithmetic of stage_rows (64-bit multiply-add, bound check, select: ~15 operations per KiB piece) was a sixth of the
+// arithmetic of staging by global pointer (64-bit multiply-add, bound check, select: ~15 operations per KiB piece) was a sixth of the
 // instructions of loops that are bound by their vector ALU work (profiles/r02_attention.json).
 template <bool TR, int NP>
 __device__ __forceinline__ void stage_offsets(int (&voff)[NP], int ld, int wave, int lane) {
@@ -191,30 +136,11 @@ __device__ __forceinline__ void stage_rows_buf(char* lds, const bf16* base, unsi
 // extent of a [nvalid, 64] head slice of a matrix with row pitch ld (elements), from the slice's first element
 __device__ __forceinline__ unsigned stage_extent(int nvalid, int ld) { return (unsigned)(((long long)(nvalid - 1) * ld + 64) * 2); }
 
-// A operand (32 rows x 16 k) read by rows: lane (row = lane&31, half h) takes 16 bytes at d = 16*st + 8*h
-__device__ __forceinline__ bf16x8 read_rows(const char* tile, int row0, int st, int lane) {
-    const int row = row0 + (lane & 31);
-    const int c = (2 * st + (lane >> 5)) ^ swz_row(row);
-    return *(const bf16x8*)(tile + row * 128 + c * 16);
-}
-
-// A operand = transpose of a row-major tile: rows of the operand are columns d = dblk*32 + (lane&31),
-// element j of lane half h is tile row  r0 + 8*(j>>2) + 4*h + (j&3)   (the k order of an accumulator
-// tile used as B operand).  TR selects the tile's swizzle.
-template <bool TR>
-__device__ __forceinline__ bf16x8 read_cols(const char* tile, int r0, int dblk, int lane) {
-    const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
-    const int h = g >> 1;
-    const int chunk = dblk * 4 + (g & 1) * 2 + (pp >> 1);
-    const int ra = r0 + 4 * h + q, rb = ra + 8;
-    const int ca = chunk ^ (TR ? swz_tr(ra) : swz_row(ra));
-    const int cb = chunk ^ (TR ? swz_tr(rb) : swz_row(rb));
-    const bf16x4 lo = lds_tr16(tile + ra * 128 + ca * 16 + (pp & 1) * 8);
-    const bf16x4 hi = lds_tr16(tile + rb * 128 + cb * 16 + (pp & 1) * 8);
-    return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
-// The same two readers with the per-lane part of the address precomputed (it does not depend on the key block): inside
+// Fragment readers.  Rows: the A operand (32 rows x 16 k) read by rows, lane (row = lane&31, half h) takes 16 bytes at
+// d = 16*st + 8*h.  Cols: the A operand = transpose of a row-major tile: rows of the operand are columns d = dblk*32 + (lane&31),
+// element j of lane half h is tile row  r0 + 8*(j>>2) + 4*h + (j&3)  (the k order of an accumulator tile used as B operand);
+// TR selects the tile's swizzle.
+// The per-lane part of the address is precomputed (it does not depend on the key block): inside
 // the loops only compile-time byte offsets remain (row0 * 128: the swizzles repeat every 16 rows), so a fragment read
 // costs no vector ALU work -- the forward loop spent 62 of its ~190 non-transcendental VALU instructions on addresses.
 //   rows: off_rows[st] = (lane&31)*128 + ((2*st + lane>>5) ^ swz_row(lane&31))*16         + row0*128 (row0 % 16 == 0)
@@ -234,16 +160,6 @@ __device__ __forceinline__ void cols_offsets(int lane, int (&off)[2], int (&offh
         off[db] = ra * 128 + ((chunk ^ (TR ? swz_tr(ra) : swz_row(ra))) << 4) + (pp & 1) * 8;
         offh[db] = rb * 128 + ((chunk ^ (TR ? swz_tr(rb) : swz_row(rb))) << 4) + (pp & 1) * 8;
     }
-}
-__device__ __forceinline__ bf16x8 read_rows_at(const char* tile, int off, int row0) {
-    return *(const bf16x8*)(tile + off + row0 * 128);
-}
-// (the asm read has no compiler-visible addressing mode: the constant part goes into its offset field by hand)
-template <int BYTES>
-__device__ __forceinline__ bf16x4 lds_tr16_imm(unsigned a) {
-    bf16x4 r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(a), "n"(BYTES) : "memory");
-    return r;
 }
 // Round 3: the ring stage is a compile-time constant too (the key / query loops are unrolled over their two stages), so the
 // stage base joins the immediate and a fragment read is `base register + offset field`, nothing else: the forward loop
@@ -274,14 +190,6 @@ __device__ __forceinline__ bf16x8 read_cols_imm(unsigned abs_lo, unsigned abs_hi
     return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
 #endif
-template <int R0>
-__device__ __forceinline__ bf16x8 read_cols_at(const char* tile, int off, int offh) {
-    const unsigned a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const char*)tile;
-    const bf16x4 lo = lds_tr16_imm<R0 * 128>(a + off);
-    const bf16x4 hi = lds_tr16_imm<R0 * 128>(a + offh);
-    return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
 // registers 8s..8s+7 of an accumulator tile -> bf16 fragment (B operand of the next MFMA)
 __device__ __forceinline__ bf16x8 pack_acc(const f32x16& a, int s) {
     bf16x8 r;
@@ -321,8 +229,10 @@ constexpr int KV_TILE = 64 * 128;  // bytes of one [64][64] bf16 tile
 // Block -> (sequence tile, head, image).  All sequence tiles of one (image, head) stream the same K / V (forward, dq)
 // or Q / dO (dk/dv) rows; placed on ONE XCD they share them through its L2 (workgroups go to XCDs round-robin by linear
 // id, so head-image hb takes the ids congruent to hb mod 8).  Returns false for the padding ids of the last group.
+// BLOCK_ROWS = sequence rows (queries, or keys for dk / dv) per block.
+template <int BLOCK_ROWS = 128>
 __device__ __forceinline__ bool attn_block(const AttnArgs& p, int& tile, int& head, int& b) {
-    const int tiles = (p.N + 127) / 128;
+    const int tiles = (p.N + BLOCK_ROWS - 1) / BLOCK_ROWS;
     const int lin = blockIdx.x, j = lin >> 3;
     tile = j % tiles;
     const int hb = (j / tiles) * 8 + (lin & 7);
@@ -391,18 +301,6 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs p) {
 #pragma unroll
     for (int i = 0; i < D; ++i)
         if (i < nblk) stage(i, smem + i * 2 * KV_TILE);
-#if TV_ATTN_SUM_MFMA
-    // row sums of P on the matrix pipe: an A operand of ones makes every row of  ones x P^T  the column sums of P^T, i.e.
-    // each lane receives sum_k P[q][k] over ALL 16 k slots (both lane halves) in every register of `lt` (only lt[0] is
-    // used).  4 more MFMAs per 64-key block against 32 v_add_f32 + a cross-half exchange: the loop is bound by its vector
-    // ALU work (~920 issue cycles per block beside 512 cycles of MFMA), the matrix pipe has the room.  The sum is taken over
-    // the bf16-rounded P that V is multiplied with (a normaliser consistent with the numerator).
-    const bf16 one_b = (bf16)1.0f;
-    const bf16x8 ones = {one_b, one_b, one_b, one_b, one_b, one_b, one_b, one_b};
-    f32x16 lt;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) lt[i] = 0.f;
-#endif
     // one 64-key block out of ring stage S (compile-time)
     auto key_block = [&](int t, auto stage_c) {
         constexpr int S = decltype(stage_c)::value;
@@ -410,9 +308,6 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs p) {
         if (t + D - 1 < nblk) vm_wait<PIECES * (D - 1)>();
         else vm_wait<0>();
         block_sync();
-#if !TV_ATTN_DMA_LATE
-        if (!(TV_ATTN_ABL & 8) && t + D < nblk) stage(t + D, smem + ((S + D) % NS) * 2 * KV_TILE);
-#endif
         f32x16 s[2];
 #pragma unroll
         for (int i = 0; i < 16; ++i) s[0][i] = s[1][i] = 0.f;
@@ -424,27 +319,20 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs p) {
         s[1] = mfma32(read_rows_imm<KB + 32 * 128>(abs_k[1]), qf[1], s[1]);
         s[1] = mfma32(read_rows_imm<KB + 32 * 128>(abs_k[2]), qf[2], s[1]);
         s[1] = mfma32(read_rows_imm<KB + 32 * 128>(abs_k[3]), qf[3], s[1]);
-#if TV_ATTN_DMA_LATE
         // the next stage's DMA pieces issue in the shadow of the eight S MFMAs (an LDS-DMA instruction holds its wave for
         // 60-180 cycles; right after the barrier all four waves paid that with the matrix pipe idle)
         __builtin_amdgcn_sched_barrier(0);
         if (!(TV_ATTN_ABL & 8) && t + D < nblk) stage(t + D, smem + ((S + D) % NS) * 2 * KV_TILE);
         __builtin_amdgcn_sched_barrier(0);
-#endif
         bf16x8 vfr[2][2][2];
-        auto read_v = [&]() {
-#pragma unroll
-            for (int db = 0; db < 2; ++db) {
-                vfr[0][0][db] = read_cols_imm<VB + 0 * 128>(abs_v[db], abs_vh[db]);
-                vfr[0][1][db] = read_cols_imm<VB + 16 * 128>(abs_v[db], abs_vh[db]);
-                vfr[1][0][db] = read_cols_imm<VB + 32 * 128>(abs_v[db], abs_vh[db]);
-                vfr[1][1][db] = read_cols_imm<VB + 48 * 128>(abs_v[db], abs_vh[db]);
-            }
-        };
-#if !TV_ATTN_V_LATE
         // V^T fragments of the whole 64-key block (transposed reads, asm): issued now, consumed after the softmax
-        read_v();
-#endif
+#pragma unroll
+        for (int db = 0; db < 2; ++db) {
+            vfr[0][0][db] = read_cols_imm<VB + 0 * 128>(abs_v[db], abs_vh[db]);
+            vfr[0][1][db] = read_cols_imm<VB + 16 * 128>(abs_v[db], abs_vh[db]);
+            vfr[1][0][db] = read_cols_imm<VB + 32 * 128>(abs_v[db], abs_vh[db]);
+            vfr[1][1][db] = read_cols_imm<VB + 48 * 128>(abs_v[db], abs_vh[db]);
+        }
         // online softmax over this lane's 32 keys (+ the other half-wave's 32); scores stay unscaled, the scale
         // rides in the exp2 FMA:  p = exp2(s*c2 - m*c2)
         const int kv0 = t * 64;
@@ -476,11 +364,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs p) {
             const float mnew = fmaxf(m, mloc);
             const float alpha = fexp2((m - mnew) * c2);
             m = mnew;
-#if TV_ATTN_SUM_MFMA
-            lt[0] *= alpha;
-#else
             l *= alpha;
-#endif
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 ot[0][i] *= alpha;
@@ -488,49 +372,16 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs p) {
             }
         }
         const float mc = m * c2;
-#if !TV_ATTN_SUM_MFMA
         float rs = 0.f;
-#endif
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const float pv = fexp2(fmaf(s[kt][r], c2, -mc));
                 s[kt][r] = pv;
-#if !TV_ATTN_SUM_MFMA
                 rs += pv;
-#endif
             }
-#if !TV_ATTN_SUM_MFMA
         l += rs;           // this lane half's keys only: the halves are added once, after the loop
-#endif
-#if TV_ATTN_V_LATE == 1
-        __builtin_amdgcn_sched_barrier(0);
-        read_v();          // 32 registers less across the softmax
-#endif
-#if TV_ATTN_V_LATE == 2
-        // V^T fragments 32 keys at a time, right before their MFMAs: 16 live registers instead of 32 held across the softmax
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) {
-            bf16x8 vh[2][2];
-#pragma unroll
-            for (int db = 0; db < 2; ++db) {
-                if (kt == 0) {
-                    vh[0][db] = read_cols_imm<VB + 0 * 128>(abs_v[db], abs_vh[db]);
-                    vh[1][db] = read_cols_imm<VB + 16 * 128>(abs_v[db], abs_vh[db]);
-                } else {
-                    vh[0][db] = read_cols_imm<VB + 32 * 128>(abs_v[db], abs_vh[db]);
-                    vh[1][db] = read_cols_imm<VB + 48 * 128>(abs_v[db], abs_vh[db]);
-                }
-            }
-            bf16x8 pf[2] = {pack_acc(s[kt], 0), pack_acc(s[kt], 1)};
-            lds_wait_all();
-#pragma unroll
-            for (int ss = 0; ss < 2; ++ss)
-#pragma unroll
-                for (int db = 0; db < 2; ++db) ot[db] = mfma32b(vh[ss][db], pf[ss], ot[db]);
-        }
-#else
         lds_wait_all();
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
@@ -539,18 +390,10 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs p) {
                 const bf16x8 pf = pack_acc(s[kt], ss);
 #pragma unroll
                 for (int db = 0; db < 2; ++db) ot[db] = mfma32b(vfr[kt][ss][db], pf, ot[db]);
-#if TV_ATTN_SUM_MFMA
-                lt = mfma32b(ones, pf, lt);
-#endif
             }
-#endif
     };
     ring_for<NS>(nblk, key_block);
-#if TV_ATTN_SUM_MFMA
-    l = lt[0];
-#else
     l = xhalf_sum(l);
-#endif
     if (q_ok) {
         const float inv = 1.0f / l;
         bf16* orow = p.out + ((size_t)b * p.N + qi) * C + head * 64;
@@ -574,18 +417,6 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs p) {
 // bytes for twice the matrix work.  The 64-key stage is walked as two 32-key halves so that only two S tiles are alive
 // (one per query tile): registers ~190, two blocks per CU.
 // ------------------------------------------------------------------------------------------------
-template <int BLOCK_Q>
-__device__ __forceinline__ bool attn_block_q(const AttnArgs& p, int& tile, int& head, int& b) {
-    const int tiles = (p.N + BLOCK_Q - 1) / BLOCK_Q;
-    const int lin = blockIdx.x, j = lin >> 3;
-    tile = j % tiles;
-    const int hb = (j / tiles) * 8 + (lin & 7);
-    if (hb >= p.heads * p.B) return false;
-    head = hb % p.heads;
-    b = hb / p.heads;
-    return true;
-}
-
 #ifndef TV_ATTN_FWD64_OCC
 #define TV_ATTN_FWD64_OCC 3   // waves per SIMD the register allocation must leave room for (176 registers / 2 waves: 1.813 ms; capped at 168 / 3 waves, 7 dwords spilled: 1.693 ms)
 #endif
@@ -594,7 +425,7 @@ __global__ __launch_bounds__(256, TV_ATTN_FWD64_OCC) void attn_fwd64_kernel(cons
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int tile_x, head, b;
-    if (!attn_block_q<256>(p, tile_x, head, b)) return;
+    if (!attn_block<256>(p, tile_x, head, b)) return;
     const int C = p.heads * 64;
     const size_t ld = (size_t)3 * C;
     const bf16* qbase = p.qkv + (size_t)b * p.N * ld + head * 64;
@@ -863,7 +694,6 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnArgs p) {
 #pragma unroll
     for (int i = 0; i < D; ++i)
         if (i < nblk) stage(i, smem + i * 2 * KV_TILE);
-#if TV_ATTN_DELTA_MFMA
     // dP - delta out of the MFMA chain: one more k-step whose A operand holds 1 in k slots 0..2 (every key row) and whose B
     // operand holds -delta of the lane's query as three bf16 pieces (hi + mid + lo = the fp32 value to 2^-24) in the same
     // slots.  The query is on the LANE here, so starting the accumulator from -delta would take 16 register broadcasts per
@@ -883,7 +713,6 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnArgs p) {
             dl_b[2] = d2;
         }
     }
-#endif
     // 32 keys (half KT of a 64-key block) out of ring stage S, both compile-time
     auto half_block = [&](int t, auto stage_c, auto kt_c) {
         constexpr int S = decltype(stage_c)::value, KT = decltype(kt_c)::value;
@@ -891,9 +720,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnArgs p) {
         f32x16 s, dp;
 #pragma unroll
         for (int i = 0; i < 16; ++i) s[i] = dp[i] = 0.f;
-#if TV_ATTN_DELTA_MFMA
         dp = mfma32(dl_a, dl_b, dp);
-#endif
         s = mfma32(read_rows_imm<KB + RO>(abs_r[0]), qf[0], s);
         dp = mfma32(read_rows_imm<VB + RO>(abs_r[0]), gf[0], dp);
         s = mfma32(read_rows_imm<KB + RO>(abs_r[1]), qf[1], s);
@@ -902,13 +729,11 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnArgs p) {
         dp = mfma32(read_rows_imm<VB + RO>(abs_r[2]), gf[2], dp);
         s = mfma32(read_rows_imm<KB + RO>(abs_r[3]), qf[3], s);
         dp = mfma32(read_rows_imm<VB + RO>(abs_r[3]), gf[3], dp);
-#if TV_ATTN_DMA_LATE
         if constexpr (KT == 0) {   // the next stage's DMA pieces in the shadow of the first S / dP MFMAs (see attn_fwd_kernel)
             __builtin_amdgcn_sched_barrier(0);
             if (!(TV_ATTN_ABL & 8) && t + D < nblk) stage(t + D, smem + ((S + D) % NS) * 2 * KV_TILE);
             __builtin_amdgcn_sched_barrier(0);
         }
-#endif
         bf16x8 kfr[2][2];   // K^T fragments (transposed asm reads): in flight during the exponentials
 #pragma unroll
         for (int db = 0; db < 2; ++db) {
@@ -925,11 +750,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnArgs p) {
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {   // dS^T (without the factor `scale`)
-#if TV_ATTN_DELTA_MFMA
             s[r] = fexp2(fmaf(s[r], c2, nl)) * dp[r];
-#else
-            s[r] = fexp2(fmaf(s[r], c2, nl)) * (dp[r] + nd);
-#endif
         }
         lds_wait_all();
 #pragma unroll
@@ -944,9 +765,6 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnArgs p) {
         if (t + D - 1 < nblk) vm_wait<PIECES * (D - 1)>();
         else vm_wait<0>();
         block_sync();
-#if !TV_ATTN_DMA_LATE
-        if (!(TV_ATTN_ABL & 8) && t + D < nblk) stage(t + D, smem + ((S + D) % NS) * 2 * KV_TILE);
-#endif
         half_block(t, stage_c, ic<0>{});
         half_block(t, stage_c, ic<1>{});
     };
@@ -1061,15 +879,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnArgs p) {
         nd[1] = *(const f32x4*)(abs_st + STB + 128 + 32);
         nd[2] = *(const f32x4*)(abs_st + STB + 128 + 64);
         nd[3] = *(const f32x4*)(abs_st + STB + 128 + 96);
-#if TV_ATTN_DKV_ACCINIT
         // the query is on the accumulator ROW here: -delta of rows 8g+4h+{0..3} is one broadcast 16-byte LDS read per g and
         // IS dP's initial accumulator as it arrives (no 16 v_add_f32 per tile, no second copy in registers)
 #pragma unroll
         for (int r = 0; r < 16; ++r) dp[r] = nd[r >> 2][r & 3];
-#else
-#pragma unroll
-        for (int i = 0; i < 16; ++i) dp[i] = 0.f;
-#endif
         s = mfma32(read_rows_imm<QB>(abs_r[0]), kf[0], s);
         dp = mfma32(read_rows_imm<GB>(abs_r[0]), vf[0], dp);
         s = mfma32(read_rows_imm<QB>(abs_r[1]), kf[1], s);
@@ -1078,13 +891,11 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnArgs p) {
         dp = mfma32(read_rows_imm<GB>(abs_r[2]), vf[2], dp);
         s = mfma32(read_rows_imm<QB>(abs_r[3]), kf[3], s);
         dp = mfma32(read_rows_imm<GB>(abs_r[3]), vf[3], dp);
-#if TV_ATTN_DMA_LATE
         if constexpr (U == 0) {   // the next stage's pieces in the shadow of the stage's first S / dP MFMAs
             __builtin_amdgcn_sched_barrier(0);
             if (!(TV_ATTN_ABL & 8) && t + D < ntile) stage(t + D, smem + ((S + D) % NS) * DKV_STAGE);
             __builtin_amdgcn_sched_barrier(0);
         }
-#endif
         bf16x8 gfr[2][2], qfr[2][2];   // dO^T and Q^T fragments (transposed asm reads)
 #pragma unroll
         for (int db = 0; db < 2; ++db) {
@@ -1098,11 +909,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnArgs p) {
         for (int r = 0; r < 16; ++r) {
             const float pv = fexp2(fmaf(s[r], c2, nl[r >> 2][r & 3]));
             s[r] = pv;
-#if TV_ATTN_DKV_ACCINIT
             dp[r] = pv * dp[r];
-#else
-            dp[r] = pv * (dp[r] + nd[r >> 2][r & 3]);
-#endif
         }
         lds_wait_all();
 #pragma unroll
@@ -1126,9 +933,6 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnArgs p) {
             vm_wait<0>();
         }
         block_sync();
-#if !TV_ATTN_DMA_LATE
-        if (!(TV_ATTN_ABL & 8) && t + D < ntile) stage(t + D, smem + ((S + D) % NS) * DKV_STAGE);
-#endif
         query_tile(t, stage_c, ic<0>{});
         if constexpr (DKV_QS > 1) {
             if ((t * DKV_QS + 1) * 32 < p.N) query_tile(t, stage_c, ic<1>{});

@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+#include <utility>
+
 #include "../../include/transvae_hip.h"
 
 typedef __bf16 bf16;
@@ -180,12 +183,45 @@ __device__ __forceinline__ void buffer_load_lds16(const void* base, unsigned byt
                                              TV_LDS(lds), 16, voff, soff, 0, 0);
 #endif
 }
-// the same with the non-temporal cache policy (aux bit 1): operand bytes a launch reads once
-__device__ __forceinline__ void buffer_load_lds16_nt(const void* base, unsigned bytes, char* lds, int voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000),
-                                             TV_LDS(lds), 16, voff, soff, 0, 2);
-#endif
+
+// ---------------------------------------------------------------------------
+// waits and transposed LDS reads shared by the MFMA kernels
+// ---------------------------------------------------------------------------
+// counted wait: at most N of this wave's vector-memory instructions (LDS-DMA pieces, loads, stores) still in flight
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+// ds_read_b64_tr_b16 through inline asm: with the builtin, hipcc (ROCm 7.2) puts an s_waitcnt vmcnt(0) in front of every
+// transposed read while an LDS-DMA is in flight (it does not for plain ds_read_b128), which serialises the DMA ring with
+// compute.  An asm read is invisible to that pass; callers wait for its completion with lds_wait_all() before use
+// (cdna_hip_programming.md section 5.7, rule 18).
+__device__ __forceinline__ bf16x4 lds_tr16(unsigned lds_addr) {
+    bf16x4 r;
+    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(lds_addr) : "memory");
+    return r;
+}
+// (the asm read has no compiler-visible addressing mode: a compile-time part of the address goes into its offset field by hand)
+template <int OFF>
+__device__ __forceinline__ bf16x4 lds_tr16_imm(unsigned lds_addr) {
+    static_assert(OFF >= 0 && OFF < 65536, "ds offset field is 16 bits");
+    bf16x4 r;
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(lds_addr), "n"(OFF) : "memory");
+    return r;
+}
+__device__ __forceinline__ void lds_wait_all() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// f(integral_constant<int, I>) for I = 0 .. N-1: an unrolled loop whose index is usable as a template argument
+template <class F, int... I>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
 // ---------------------------------------------------------------------------

@@ -24,16 +24,11 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv3x3_halo_kernel(const Igemm
     constexpr int A_PIECES = (HP * 8 + 63) / 64;             // 1 KiB DMA pieces per halo chunk (8 pixels each)
     constexpr int WTM = BM / WGM, WTN = BN / WGN, MF = WTM / 16, NF = WTN / 16;
     constexpr bool PIPE_ALL = (MF + NF) * 4 * (BK / 32) <= (NW == 4 && BM == 256 ? 128 : 80);   // (one wave per SIMD owns 512 registers)
-    // Loader waves.  Waves w and w+4 of an 8-wave block share a SIMD and run in lockstep between barriers; a DMA issued by
-    // all eight at the same point of the MFMA stream queues ~120 cycles at the address pipe (64 B/clk per CU) and stalls
-    // BOTH waves of every SIMD.  In the pipelined loop only waves 0 .. NWL-1 issue DMAs: while one of them waits at the
-    // address pipe its partner keeps the MFMA pipe busy.
-    constexpr int NWL = (NW == 8 && PIPE_ALL && !TV_NO_PIPE2 && !TV_NO_LOADER_SPLIT) ? 4 : NW;
-    constexpr int A_IT = (A_PIECES + NWL - 1) / NWL;         // halo pieces per loader wave and chunk
+    constexpr int A_IT = (A_PIECES + NW - 1) / NW;           // halo pieces per wave and chunk (every wave issues DMAs)
     constexpr int A_BYTES = A_PIECES * 1024, B_BYTES = BN * BK * 2;
-    constexpr int B_INSTR = BN / 8, B_IT = B_INSTR / NWL;
+    constexpr int B_INSTR = BN / 8, B_IT = B_INSTR / NW;
     static_assert(BST == 2 || BST == 3, "weight ring depth");
-    static_assert(B_INSTR % NWL == 0 && WTM % 16 == 0 && WTN % 16 == 0, "tile shape");
+    static_assert(B_INSTR % NW == 0 && WTM % 16 == 0 && WTN % 16 == 0, "tile shape");
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     TV_PROBE_DECL
@@ -96,30 +91,26 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv3x3_halo_kernel(const Igemm
 
     // where the registers allow, the offsets are computed once (the recomputation is ~12 VALU operations per piece in the
     // middle of the MFMA stream)
-    constexpr bool VOFF_REGS = TV_HALO_VOFF_REGS && (MF * NF * 4 + (MF + NF) * 8 <= 160 || BST == 3 || !PIPE_ALL);   // (256x192, ring 2 would spill)
+    constexpr bool VOFF_REGS = MF * NF * 4 + (MF + NF) * 8 <= 160 || BST == 3 || !PIPE_ALL;   // (256x192, ring 2 would spill)
     int a_voff_r[VOFF_REGS ? A_IT : 1], b_voff_r[VOFF_REGS ? B_IT : 1];
     if constexpr (VOFF_REGS) {
 #pragma unroll
-        for (int it = 0; it < A_IT; ++it) a_voff_r[it] = a_voff_of(it * NWL + wave);
+        for (int it = 0; it < A_IT; ++it) a_voff_r[it] = a_voff_of(it * NW + wave);
 #pragma unroll
-        for (int it = 0; it < B_IT; ++it) b_voff_r[it] = b_voff_of(it * NWL + wave);
+        for (int it = 0; it < B_IT; ++it) b_voff_r[it] = b_voff_of(it * NW + wave);
     }
-    auto issue_a = [&](char* dst, int it, int ch) {   // piece `it` of this (loader) wave, channel chunk ch
+    auto issue_a = [&](char* dst, int it, int ch) {   // piece `it` of this wave, channel chunk ch
 #ifdef TV_ABL_NO_DMA
         return;
 #endif
-        const int j = it * NWL + wave;
-#if TV_HALO_A_NT
-        if (j < A_PIECES) buffer_load_lds16_nt(p.x, p.x_bytes, dst + j * 1024, VOFF_REGS ? a_voff_r[VOFF_REGS ? it : 0] : a_voff_of(j), ch * (BK * 2));
-#else
+        const int j = it * NW + wave;
         if (j < A_PIECES) buffer_load_lds16(p.x, p.x_bytes, dst + j * 1024, VOFF_REGS ? a_voff_r[VOFF_REGS ? it : 0] : a_voff_of(j), ch * (BK * 2));
-#endif
     };
     auto issue_b_piece = [&](char* dst, int it, int koff) {
 #ifdef TV_ABL_NO_DMA
         return;
 #endif
-        buffer_load_lds16(p.w, p.w_bytes, dst + (it * NWL + wave) * 1024, VOFF_REGS ? b_voff_r[VOFF_REGS ? it : 0] : b_voff_of(it * NWL + wave), koff);
+        buffer_load_lds16(p.w, p.w_bytes, dst + (it * NW + wave) * 1024, VOFF_REGS ? b_voff_r[VOFF_REGS ? it : 0] : b_voff_of(it * NW + wave), koff);
     };
     auto issue_b = [&](char* dst, int tap, int ch) {
         const int koff = (tap * p.c_in + ch * BK) * 2;
@@ -218,9 +209,8 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv3x3_halo_kernel(const Igemm
     // phases of step t.  A wave waits (counted vmcnt) at the END of each load phase for everything it issued in EARLIER load
     // phases: slab t+2 has landed and is visible (next barrier) one full step before g0 reads it.  The halo pieces of chunk
     // c+1 go out during taps 0-5 of chunk c into the buffer last read at the final tap of chunk c-1.
-    constexpr bool PP = TV_HALO_PP && NW == 8 && PIPE_ALL && BST == 3;
+    constexpr bool PP = NW == 8 && PIPE_ALL && BST == 3;
     if constexpr (PP) {
-        static_assert(NWL == NW, "ping-pong: every wave loads");
         constexpr int ATAPS = 6, A_PT = (A_IT + ATAPS - 1) / ATAPS;
         static_assert(A_PT == 1, "one halo piece per wave and tap");
         constexpr auto nsure = [](int tap) { return (tap >= 0 && tap < ATAPS && tap < A_IT && (tap + 1) * NW <= A_PIECES) ? 1 : 0; };
@@ -231,140 +221,32 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv3x3_halo_kernel(const Igemm
         issue_b(b_buf, 0, 0);
         issue_b(b_buf + B_BYTES, 1, 0);
         wait_vmcnt<0>();
-#if TV_HALO_P8
-        // Round 3: a tap step in FOUR phases of 12 MFMAs (quadrants: 2 fragment rows x 3 fragment columns x both halves of
-        // BK), each with its own small load section -- 4-10 fragment reads and ONE DMA piece -- instead of one load phase of 20
-        // reads + a burst of 3-4 pieces against one MFMA phase of 48: the pieces of a burst queue at the address pipe
-        // (~150 wave-cycles each against ~60 alone; the ablation of the two-phase form: 2.19 ms, DMA issue off 1.54), which made
-        // the load phase longer than the partner's MFMA phase.  Same ping-pong (group 1 one barrier behind), same ring, same
-        // counted wait (at the end of the step's last load section), same results bit for bit; the structure that took the
-        // generic 256-row tiles from 0.345 to 0.307 ms (igemm_nt.hip, eight-phase loop).
-        //   L1 reads A0 + B_lo, issues weight piece 0 | L2 reads B_hi, piece 1 | L3 reads A1, piece 2 | L4 reads B_lo, halo piece, wait
-        //   hazards: the slot of slab t+2 was last read in L4 of step t-1 by either group, complete (lgkmcnt) before the barrier
-        //   that ends that section; the same group's L1 of step t follows two barriers later.
-        static_assert(MF % 2 == 0 && NF % 2 == 0 && B_IT <= 3 && TV_PP_NM == 0, "halo eight-phase loop: one weight piece per load section");
-        constexpr int MH = MF / 2, NH = NF / 2;
-        __builtin_amdgcn_s_barrier();                 // the prologue's pieces have landed for every wave
-        if (grp == 1) __builtin_amdgcn_s_barrier();   // the stagger: group 1 runs one barrier behind
-        int bcur = 0;
-        bf16x8 qa[2][MH], qb[2][NH];
-        for (int ch = 0; ch < cch; ++ch) {
-            const char* acur = a_buf + (ch & 1) * A_BYTES;
-            char* anxt = a_buf + ((ch + 1) & 1) * A_BYTES;
-            const bool more = ch + 1 < cch;
-            static_for<0, 9>([&](auto tap_c) {
-                constexpr int tap = decltype(tap_c)::value;
-                constexpr int toff = (tap / 3) * HWD + (tap % 3);
-                const char* const bslot = b_buf + bcur * B_BYTES;
-                char* const bfill = b_buf + ((bcur + 2 >= BST) ? bcur + 2 - BST : bcur + 2) * B_BYTES;
-                const bool b_go = (tap + 2 < 9) || more;
-                const int b_koff = ((tap + 2 < 9) ? (tap + 2) * p.c_in + ch * BK : (tap + 2 - 9) * p.c_in + (ch + 1) * BK) * 2;
-                int hpb = hp_base;
-                asm volatile("" : "+v"(hpb));   // pin the address arithmetic to this tap
-                auto rd_a = [&](auto a_c) {
-                    constexpr int a = decltype(a_c)::value;
-#pragma unroll
-                    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                        for (int i = 0; i < MH; ++i) {
-                            const int hp = hpb + (MH * a + i) * HWD + toff;
-                            qa[kk][i] = *(const bf16x8*)(acur + hp * (BK * 2) + (((kk * 4 + fq) ^ (hp & 7)) << 4));
-                        }
-                };
-                auto rd_b = [&](auto b_c) {
-                    constexpr int b = decltype(b_c)::value;
-#pragma unroll
-                    for (int kk = 0; kk < 2; ++kk) {
-                        const int coff = ((kk * 4 + fq) ^ sw) * 16;
-#pragma unroll
-                        for (int j = 0; j < NH; ++j) qb[kk][j] = *(const bf16x8*)(bslot + b_row_off + bfrag_off(NH * b + j) * (BK * 2) + coff);
-                    }
-                };
-                auto close_load = [&]() {
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_s_barrier();
-                    __builtin_amdgcn_sched_barrier(0);
-                };
-                auto mm = [&](auto a_c, auto b_c) {
-                    constexpr int a = decltype(a_c)::value, b = decltype(b_c)::value;
-                    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                        for (int i = 0; i < MH; ++i)
-#pragma unroll
-                            for (int j = 0; j < NH; ++j)
-                                acc[MH * a + i][NH * b + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qb[kk][j], qa[kk][i], acc[MH * a + i][NH * b + j], 0, 0, 0);
-                    __builtin_amdgcn_s_setprio(0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_s_barrier();
-                    __builtin_amdgcn_sched_barrier(0);
-                };
-                using I0 = std::integral_constant<int, 0>;
-                using I1 = std::integral_constant<int, 1>;
-                rd_b(I0{});
-                __builtin_amdgcn_sched_barrier(0);
-                rd_a(I0{});
-                __builtin_amdgcn_sched_barrier(0);
-                if (0 < B_IT && b_go) issue_b_piece(bfill, 0 < B_IT ? 0 : 0, b_koff);
-                close_load();
-                mm(I0{}, I0{});
-                rd_b(I1{});
-                __builtin_amdgcn_sched_barrier(0);
-                if (1 < B_IT && b_go) issue_b_piece(bfill, 1 < B_IT ? 1 : 0, b_koff);
-                close_load();
-                mm(I0{}, I1{});
-                rd_a(I1{});
-                __builtin_amdgcn_sched_barrier(0);
-                if (2 < B_IT && b_go) issue_b_piece(bfill, 2 < B_IT ? 2 : 0, b_koff);
-                close_load();
-                mm(I1{}, I1{});
-                rd_b(I0{});
-                __builtin_amdgcn_sched_barrier(0);
-                if (tap < ATAPS && tap < A_IT && more) issue_a(anxt, tap, ch + 1);
-                // in flight may stay, in issue order: [the previous step's halo piece] [this step's weight pieces] [this step's
-                // halo piece]: the slab of the NEXT step (issued one step ago) has landed
-                if (more) wait_vmcnt<nsure(tap - 1) + B_IT + nsure(tap)>();
-                else if (tap + 2 < 9) wait_vmcnt<B_IT>();
-                else wait_vmcnt<0>();
-                close_load();
-                mm(I1{}, I0{});
-                bcur = (bcur + 1 == BST) ? 0 : bcur + 1;
-            });
-        }
-        if (grp == 0) __builtin_amdgcn_s_barrier();   // (both groups have passed the same number of barriers)
-#else
         if (grp == 1) __builtin_amdgcn_s_barrier();   // the stagger: group 1 runs one phase behind
         int bcur = 0;
         for (int ch = 0; ch < cch; ++ch) {
             const char* acur = a_buf + (ch & 1) * A_BYTES;
             char* anxt = a_buf + ((ch + 1) & 1) * A_BYTES;
             const bool more = ch + 1 < cch;
-            static_for<0, 9>([&](auto tap_c) {
+            static_for<9>([&](auto tap_c) {
                 constexpr int tap = decltype(tap_c)::value;
                 constexpr int toff = (tap / 3) * HWD + (tap % 3);
                 const char* const bslot = b_buf + bcur * B_BYTES;
                 char* const bfill = b_buf + ((bcur + 2 >= BST) ? bcur + 2 - BST : bcur + 2) * B_BYTES;
                 // ---- load phase --------------------------------------------------------------------------------------------
-                constexpr int NM = TV_PP_NM < B_IT ? TV_PP_NM : B_IT, NL = B_IT - NM;   // slab pieces from the MFMA / load phase
                 const bool b_go = (tap + 2 < 9) || more;
                 const int b_koff = ((tap + 2 < 9) ? (tap + 2) * p.c_in + ch * BK : (tap + 2 - 9) * p.c_in + (ch + 1) * BK) * 2;
-                // The weight pieces go out FIRST, the halo piece (HBM latency) last: vmcnt retires in issue order, so a slow halo
-                // piece in front of them would hold back the wait for the (L2-resident) weight slab behind it.
+                // The DMA pieces of the phase (issued behind its fragment reads).  The weight pieces go out FIRST, the halo piece
+                // (HBM latency) last: vmcnt retires in issue order, so a slow halo piece in front of them would hold back the wait
+                // for the (L2-resident) weight slab behind it.
                 auto load_dma = [&]() {
                     if (b_go) {
 #pragma unroll
-                        for (int it = 0; it < NL; ++it) issue_b_piece(bfill, it, b_koff);
+                        for (int it = 0; it < B_IT; ++it) issue_b_piece(bfill, it, b_koff);
                     }
                     if (tap < ATAPS && tap < A_IT && more) issue_a(anxt, tap, ch + 1);
                 };
                 __builtin_amdgcn_s_barrier();
                 TV_T(1);
-                if constexpr (TV_PP_DMA_FIRST == 1) {
-                    load_dma();
-                    __builtin_amdgcn_sched_barrier(0);
-                }
                 int hpb = hp_base;
                 asm volatile("" : "+v"(hpb));   // pin the address arithmetic to this tap
 #ifndef TV_ABL_NO_LDSREAD
@@ -375,23 +257,9 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv3x3_halo_kernel(const Igemm
                         const int hp = hpb + i * HWD + toff;
                         fa[kk][i] = *(const bf16x8*)(acur + hp * (BK * 2) + (((kk * 4 + fq) ^ (hp & 7)) << 4));
                     }
-                    if constexpr (TV_PP_DMA_FIRST == 2) {   // threaded: a DMA piece after each group of reads
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (b_go && kk < NL) issue_b_piece(bfill, kk, b_koff);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
                     const int coff = ((kk * 4 + fq) ^ sw) * 16;
 #pragma unroll
                     for (int j = 0; j < NF; ++j) fb[kk][j] = *(const bf16x8*)(bslot + b_row_off + bfrag_off(j) * (BK * 2) + coff);
-                    if constexpr (TV_PP_DMA_FIRST == 2) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (kk == 0) {
-                            if (b_go && 2 < NL) issue_b_piece(bfill, 2, b_koff);
-                        } else if (tap < ATAPS && tap < A_IT && more) {
-                            issue_a(anxt, tap, ch + 1);
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
                 }
 #else
                 if (tap == 0 && ch == 0) {
@@ -403,40 +271,27 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv3x3_halo_kernel(const Igemm
 #endif
                 __builtin_amdgcn_sched_barrier(0);
                 TV_T(3);
-                if constexpr (TV_PP_DMA_FIRST == 0) {
-                    load_dma();
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                load_dma();
+                __builtin_amdgcn_sched_barrier(0);
                 TV_T(2);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // fragments in registers: the slot may be refilled two barriers on
                 // The weight pieces of the PREVIOUS load phase (and of the MFMA phase after it) have landed; still in flight may be,
                 // in issue order: [that phase's halo piece] [this phase's weight pieces] [this phase's halo piece].  The halo
                 // pieces of a chunk are all retired by tap 7 (taps 6-8 issue none).
-                if (more) wait_vmcnt<nsure(tap - 1) + NL + nsure(tap)>();
-                else if (tap + 2 < 9) wait_vmcnt<NL>();
+                if (more) wait_vmcnt<nsure(tap - 1) + B_IT + nsure(tap)>();
+                else if (tap + 2 < 9) wait_vmcnt<B_IT>();
                 else wait_vmcnt<0>();
                 TV_T(0);
                 // ---- MFMA phase --------------------------------------------------------------------------------------------
                 __builtin_amdgcn_s_barrier();
                 TV_T(5);
-#ifndef TV_PP_NOPRIO
                 __builtin_amdgcn_s_setprio(1);
-#endif
-                constexpr int NMF2 = 2 * MF * NF, MGAP = NM > 0 ? NMF2 / (NM + 1) : NMF2 + 1;
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
                     for (int i = 0; i < MF; ++i)
 #pragma unroll
-                        for (int j = 0; j < NF; ++j) {
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[kk][j], fa[kk][i], acc[i][j], 0, 0, 0);
-                            const int idx = (kk * MF + i) * NF + j;
-                            if (NM > 0 && idx % MGAP == MGAP - 1 && idx / MGAP < NM) {
-                                __builtin_amdgcn_sched_barrier(0);
-                                if (b_go) issue_b_piece(bfill, NL + idx / MGAP, b_koff);
-                                __builtin_amdgcn_sched_barrier(0);
-                            }
-                        }
+                        for (int j = 0; j < NF; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[kk][j], fa[kk][i], acc[i][j], 0, 0, 0);
                 __builtin_amdgcn_s_setprio(0);
                 __builtin_amdgcn_sched_barrier(0);
                 TV_T(4);
@@ -444,19 +299,18 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv3x3_halo_kernel(const Igemm
             });
         }
         if (grp == 0) __builtin_amdgcn_s_barrier();   // (both groups have passed the same number of barriers)
-#endif
-    } else if constexpr (PIPE_ALL && !TV_NO_PIPE2) {
+    } else if constexpr (PIPE_ALL) {
         // Register-pipelined like the generic kernel: two half-step (32-deep) fragment sets per wave; the block barrier sits
         // between the halves of a step, when every wave has read all of step t.  After it the weight slot of step t is
         // refilled with step t+BST and the halo pieces of the next chunk go out (taps 0-5), threaded between the MFMAs of
-        // the loader waves.
+        // every wave.
         //   DMA order per step: [slab pieces x B_IT, halo pieces x <= A_PT].  At the barrier of step t slab t+1 must have
         //   landed: BST 2: only the halo pieces of step t-1 are younger;  BST 3: halo(t-2), slab(t+2), halo(t-1) are.
         constexpr int ATAPS = 6, A_PT = (A_IT + ATAPS - 1) / ATAPS;
-        constexpr auto nsure = [](int tap) {   // halo pieces of a tap that every loader wave issues
+        constexpr auto nsure = [](int tap) {   // halo pieces of a tap that every wave issues
             int n = 0;
             for (int it = tap * A_PT; it < tap * A_PT + A_PT; ++it)
-                if (tap >= 0 && tap < ATAPS && it < A_IT && (it + 1) * NWL <= A_PIECES) ++n;
+                if (tap >= 0 && tap < ATAPS && it < A_IT && (it + 1) * NW <= A_PIECES) ++n;
             return n;
         };
         constexpr int HMF = MF * NF, NIS = B_IT + A_PT, HGAP = HMF / NIS;
@@ -509,11 +363,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv3x3_halo_kernel(const Igemm
 #endif
             }
         };
-        auto mfma_half = [&](const bf16x8 (&fa)[MF], const bf16x8 (&fb)[NF], auto issue, auto rd, auto phase_c) {
-            // DMA slots: waves 4-7 (PH = 1) issue half a gap before waves 0-3, so that the eight waves of a block do not
-            // queue at the address pipe at the same MFMA index (two code copies; a per-wave branch costs more than it saves)
-            constexpr int PH = decltype(phase_c)::value;
-            constexpr int SLOT = PH ? (HGAP - 1) / 2 : HGAP - 1;
+        auto mfma_half = [&](const bf16x8 (&fa)[MF], const bf16x8 (&fb)[NF], auto issue, auto rd) {
 #pragma unroll
             for (int i = 0; i < MF; ++i)
 #pragma unroll
@@ -529,23 +379,22 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv3x3_halo_kernel(const Igemm
                         rd(idx / RGAP);
                         __builtin_amdgcn_sched_barrier(0);
                     }
-                    if (idx % HGAP == SLOT && idx / HGAP < NIS) {
+                    if (idx % HGAP == HGAP - 1 && idx / HGAP < NIS) {
                         __builtin_amdgcn_sched_barrier(0);
                         issue(idx / HGAP);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
         };
-        auto run = [&](auto loader_c, auto phase_c) {
-            constexpr bool LOADER = decltype(loader_c)::value;
-            if constexpr (LOADER) {
+        // (The loop stays a lambda called once: written as plain code in the kernel body it compiles to different -- not
+        // measured -- code.)
+        auto run = [&]() {
 #pragma unroll
-                for (int it = 0; it < A_IT; ++it) issue_a(a_buf, it, 0);
+            for (int it = 0; it < A_IT; ++it) issue_a(a_buf, it, 0);
 #pragma unroll
-                for (int sl = 0; sl < BST; ++sl) issue_b(b_buf + sl * B_BYTES, sl, 0);
-                wait_vmcnt<(BST - 1) * B_IT>();
-            }
-            if (TV_SETPRIO && NW == 8 && wave >= 4) __builtin_amdgcn_s_setprio(1);
+            for (int sl = 0; sl < BST; ++sl) issue_b(b_buf + sl * B_BYTES, sl, 0);
+            wait_vmcnt<(BST - 1) * B_IT>();
+            if (NW == 8 && wave >= 4) __builtin_amdgcn_s_setprio(1);   // waves 4-7 (the arbitration losers on every SIMD) run at priority 1
             __builtin_amdgcn_s_barrier();
             read_half(a_buf, b_buf, 0, 0, f0a, f0b);
             int bcur = 0;
@@ -553,7 +402,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv3x3_halo_kernel(const Igemm
                 const char* acur = a_buf + (ch & 1) * A_BYTES;
                 char* anxt = a_buf + ((ch + 1) & 1) * A_BYTES;
                 const bool more = ch + 1 < cch;
-                static_for<0, 9>([&](auto tap_c) {
+                static_for<9>([&](auto tap_c) {
                     constexpr int tap = decltype(tap_c)::value;
                     char* const bslot = b_buf + bcur * B_BYTES;
                     const char* const bnext = b_buf + ((bcur + 1 == BST) ? 0 : bcur + 1) * B_BYTES;
@@ -562,16 +411,14 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv3x3_halo_kernel(const Igemm
                     if constexpr (RD_THREAD) asm volatile("" : "+v"(hpb));   // pin the address arithmetic to this tap (see compute)
                     if constexpr (!RD_THREAD) read_half(acur, bslot, toff, 1, f1a, f1b);
                     __builtin_amdgcn_sched_barrier(0);
-                    mfma_half(f0a, f0b, [](int) {}, [&](int k) { read_piece(acur, bslot, hpb, toff, 1, f1a, f1b, k); }, phase_c);
+                    mfma_half(f0a, f0b, [](int) {}, [&](int k) { read_piece(acur, bslot, hpb, toff, 1, f1a, f1b, k); });
                     __builtin_amdgcn_sched_barrier(0);
                     TV_T(3);
                     const bool go_on = tap < 8 || more;
                     if (go_on) {
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // my reads of step t are done: its slab slot may be refilled
-                        if constexpr (LOADER) {
-                            if (more) wait_vmcnt<(BST == 3 ? nsure(tap - 2) + B_IT : 0) + nsure(tap - 1)>();
-                            else wait_vmcnt<(BST == 3 && tap <= 6) ? B_IT : 0>();
-                        }
+                        if (more) wait_vmcnt<(BST == 3 ? nsure(tap - 2) + B_IT : 0) + nsure(tap - 1)>();
+                        else wait_vmcnt<(BST == 3 && tap <= 6) ? B_IT : 0>();
                         TV_T(0);
 #ifndef TV_ABL_NO_BARRIER
                         __builtin_amdgcn_s_barrier();
@@ -587,36 +434,22 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv3x3_halo_kernel(const Igemm
                     auto rd_next = [&](int k) {
                         if (go_on) read_piece(a_n, bnext, hpb, toff_n, 0, f0a, f0b, k);
                     };
-                    if constexpr (LOADER) {
-                        const bool b_go = (tap + BST < 9) || more;
-                        const int b_koff = ((tap + BST < 9) ? (tap + BST) * p.c_in + ch * BK : (tap + BST - 9) * p.c_in + (ch + 1) * BK) * 2;
-                        mfma_half(f1a, f1b, [&](int q) {
-                            if (q < B_IT) {
-                                if (b_go) issue_b_piece(bslot, q, b_koff);
-                            } else if (tap < ATAPS && tap * A_PT + (q - B_IT) < A_IT && more) {
-                                issue_a(anxt, tap * A_PT + (q - B_IT), ch + 1);
-                            }
-                        }, rd_next, phase_c);
-                    } else {
-                        mfma_half(f1a, f1b, [](int) {}, rd_next, phase_c);
-                    }
+                    const bool b_go = (tap + BST < 9) || more;
+                    const int b_koff = ((tap + BST < 9) ? (tap + BST) * p.c_in + ch * BK : (tap + BST - 9) * p.c_in + (ch + 1) * BK) * 2;
+                    mfma_half(f1a, f1b, [&](int q) {
+                        if (q < B_IT) {
+                            if (b_go) issue_b_piece(bslot, q, b_koff);
+                        } else if (tap < ATAPS && tap * A_PT + (q - B_IT) < A_IT && more) {
+                            issue_a(anxt, tap * A_PT + (q - B_IT), ch + 1);
+                        }
+                    }, rd_next);
                     __builtin_amdgcn_sched_barrier(0);
                     TV_T(4);
                     bcur = (bcur + 1 == BST) ? 0 : bcur + 1;
                 });
             }
         };
-        if constexpr (NWL == NW) {
-            if constexpr (NW == 8 && HGAP >= 4 && TV_DMA_STAGGER) {
-                if (wave < 4) run(std::true_type{}, std::integral_constant<int, 0>{});
-                else run(std::true_type{}, std::integral_constant<int, 1>{});
-            } else {
-                run(std::true_type{}, std::integral_constant<int, 0>{});
-            }
-        } else {
-            if (wave < NWL) run(std::true_type{}, std::integral_constant<int, 0>{});
-            else run(std::false_type{}, std::integral_constant<int, 0>{});
-        }
+        run();
     } else {
         // ---- main loop: one barrier per (chunk, tap).  The weight slab of step t + BST - 1 and one halo piece of the next
         // chunk are issued at step t, the halo piece FIRST: vmcnt counts in order, so "at most B_IT outstanding" (BST = 3)
@@ -642,22 +475,12 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv3x3_halo_kernel(const Igemm
                 const int b_koff = ((tap + LA < 9) ? (tap + LA) * p.c_in + ch * BK : (tap + LA - 9) * p.c_in + (ch + 1) * BK) * 2;
                 char* const b_dst = b_buf + bnxt * B_BYTES;
                 TV_T(2);
-    #if TV_HALO_BURST
                 if (tap < A_IT && more) issue_a(anxt, tap, ch + 1);
                 if (b_go) {
 #pragma unroll
                     for (int it = 0; it < B_IT; ++it) issue_b_piece(b_dst, it, b_koff);
                 }
                 compute(acur, b_buf + bcur * B_BYTES, (tap / 3) * HWD + (tap % 3), [](int) {});
-#else
-                compute(acur, b_buf + bcur * B_BYTES, (tap / 3) * HWD + (tap % 3), [&](int q) {
-                    if (q == 0) {
-                        if (tap < A_IT && more) issue_a(anxt, tap, ch + 1);
-                    } else if (b_go) {
-                        issue_b_piece(b_dst, q - 1, b_koff);
-                    }
-                });
-#endif
                 TV_T(4);
                 bcur = (bcur + 1 == BST) ? 0 : bcur + 1;
                 bnxt = (bnxt + 1 == BST) ? 0 : bnxt + 1;
@@ -666,7 +489,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void conv3x3_halo_kernel(const Igemm
 
     }
 
-    if (TV_SETPRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     TV_T(5);
 #ifdef TV_ABL_NO_EPI   // (ablation: main loop only)
     {
@@ -737,7 +560,7 @@ int launch_halo_impl(IgemmArgs& a, hipStream_t s) {
     // 256x192 tiles on the ping-pong loop with the 3-deep weight ring beat every other choice wherever N is a multiple of
     // 192 (tools/probes/ab_lib.py, 64 images): 384@64 1072 -> 1273 TFLOP/s over 128x128 tiles, 768@32 1394 -> 1498 and
     // 1536@16 1220 -> 1532 over 256x256 tiles
-    if (TV_HALO_PP && N % 192 == 0 && h16 && g_cfg_bn == 0 && g_halo_ring == 3 && !g_halo_w4) { bn = 192; bm = 256; }
+    if (N % 192 == 0 && h16 && g_cfg_bn == 0 && g_halo_ring == 3 && !g_halo_w4) { bn = 192; bm = 256; }
     if (g_cfg_bn == 256 && N % 256 == 0 && h16) { bn = 256; bm = 256; }
     else if (g_cfg_bn == 192 && N % 192 == 0 && h16) { bn = 192; bm = 256; }
     else if (g_cfg_bn == 128) { bn = (N % 192 == 0 && N % 128 != 0) ? 192 : 128; bm = 128; }
@@ -745,9 +568,10 @@ int launch_halo_impl(IgemmArgs& a, hipStream_t s) {
     if (bm == 256 && !h16) bm = 128;
     if (bn == 192) {
         a.tiles_n = N / 192;
-        // weight ring 3 deep only where measured faster (one N tile: res192@256/@128); 2 everywhere else
+        // 4-wave tile: weight ring 3 deep only where measured faster (one N tile: res192@256/@128), 2 everywhere else;
+        // the 8-wave tile runs the ping-pong loop, which needs the 3-deep ring, whenever the ring setting allows it
         if (bm == 256 && g_halo_w4) return launch_halo_ring<256, 192, 2, 2>(a, (g_halo_ring == 3 && a.tiles_n == 1) || g_halo_ring == 4 ? 3 : 2, s);
-        if (bm == 256) return launch_halo_ring<256, 192, 4, 2>(a, (g_halo_ring == 3 && (a.tiles_n == 1 || TV_HALO_PP)) || g_halo_ring == 4 ? 3 : 2, s);
+        if (bm == 256) return launch_halo_ring<256, 192, 4, 2>(a, (g_halo_ring == 3 || g_halo_ring == 4) ? 3 : 2, s);
         return launch_halo_ring<128, 192, 2, 2>(a, g_halo_ring == 4 ? 3 : 2, s);
     }
     if (bn == 256 && bm == 256) {
@@ -761,11 +585,6 @@ int launch_halo_impl(IgemmArgs& a, hipStream_t s) {
 
 }  // namespace
 
-#ifdef TV_EXP_GN_EPI
-extern "C" int tv_set_gn_epi_probe(void* dev_buf) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_gn_epi_buf), &dev_buf, sizeof(void*)) == hipSuccess ? 0 : 1;
-}
-#endif
 namespace tvi {
 int launch_halo(IgemmArgs& a, hipStream_t s) { return launch_halo_impl(a, s); }
 #ifdef TV_PROBE

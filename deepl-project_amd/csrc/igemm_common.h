@@ -68,59 +68,17 @@ int set_halo_probe(void* dev_buf);
 namespace {
 using namespace tvi;
 
-#ifndef TV_NO_PIPE2
-#define TV_NO_PIPE2 0
-#endif
-#ifndef TV_NO_LOADER_SPLIT
-#define TV_NO_LOADER_SPLIT 1   // DMA from waves 0-3 only (8-wave halo tiles): measured slower, kept for A/B
-#endif
-#ifndef TV_HALO_VOFF_REGS
-#define TV_HALO_VOFF_REGS 1
-#endif
-#ifndef TV_HALO_BURST
-#define TV_HALO_BURST 1       // 256x256 halo tile (single fragment set): DMA burst after the barrier, measured +5 % over threading
-#endif
-#ifndef TV_GENERIC_BURST
-#define TV_GENERIC_BURST 1    // same for the generic 256x256 tile (A/B on the 768-channel linear layers: +2-5 %)
-#endif
 #ifndef TV_PIPE_ALL_MAX
 #define TV_PIPE_ALL_MAX 80   // fragment registers (both halves) up to which the generic kernel runs the pipelined loop
 #endif
-#ifndef TV_DMA_STAGGER
-#define TV_DMA_STAGGER 0    // two code copies with shifted DMA slots for waves 0-3 / 4-7: measured -3 % (register pressure)
-#endif
 #ifndef TV_RD_THREAD
 #define TV_RD_THREAD 0
-#endif
-#ifndef TV_SETPRIO
-#define TV_SETPRIO 1           // waves 4-7 (the arbitration losers on every SIMD) run at priority 1
-#endif
-#ifndef TV_HALO_PP
-#define TV_HALO_PP 1       // wave-group ping-pong main loop of the 8-wave halo tiles with a 3-deep weight ring (see conv3x3_halo_kernel):
-#endif                     // +8-10 % on the 192-channel 3x3 layers over the lockstep pipelined loop (tools/probes/ab_lib.py)
-#ifndef TV_P8_B0PF
-#define TV_P8_B0PF 1       // eight-phase GEMM loop: B0 fragments resident for both of their quadrants, the next K-step's read in phase 4
-#endif
-#ifndef TV_HALO_A_NT
-#define TV_HALO_A_NT 0     // halo pieces (activations, read ~1.1 times per launch) with the non-temporal policy: A/B in item 24
-#endif
-#ifndef TV_HALO_P8
-#define TV_HALO_P8 0       // halo ping-pong loop in four phases of 12 MFMAs per tap step (one DMA piece per load section) instead of two: measured 8-11 % SLOWER (profiles/r03_kernel_experiments.txt item 15), kept for A/B
-#endif
-#ifndef TV_PP_NM
-#define TV_PP_NM 0         // ping-pong: weight-slab DMA pieces (of B_IT per wave and step) issued from the MFMA phase
-#endif
-#ifndef TV_PP_DMA_FIRST
-#define TV_PP_DMA_FIRST 0  // ping-pong: DMA pieces of a load phase before (1) or after (0) its fragment reads; 2 = threaded between them
 #endif
 #ifndef TV_GENERIC_DPHASE
 #define TV_GENERIC_DPHASE 1   // generic pipelined loop: DMA slots staggered by wave through a run-time phase (scalar branches in the MFMA stream)
 #endif
 #ifndef TV_PERSIST_DRAIN
 #define TV_PERSIST_DRAIN 1    // persistent column loop (off by default, tv_set_igemm_persist): 1 = open every tile with vmcnt(0) -- drains the previous tile's stores too, no hand-counted wait; 0 = the counted vmcnt(NST) form, for A/B
-#endif
-#ifndef TV_NO_PINGPONG
-#define TV_NO_PINGPONG 1   // ping-pong main loop of the 8-wave tiles: measured, not (yet) a win -- see DESIGN.md
 #endif
 
 // Order of the output channels inside a wave's WTN-wide weight slab.  The MFMA is issued as D' = W_frag x A_frag^T: lane
@@ -132,22 +90,8 @@ __device__ __forceinline__ constexpr int bfrag_off(int j) { return (j >> 1) * 32
 __device__ __forceinline__ int bfrag_lane_row(int fi) { return (fi >> 2) * 8 + (fi & 3); }           // operand row fi of fragment 0
 __device__ __forceinline__ int bfrag_reader(int rl) { return (((rl & 31) >> 3) << 2) | (rl & 3); }    // operand row that reads local channel rl
 
-// f(integral_constant<int, I>) for I = I0 .. N-1: an unrolled loop whose index is usable as a template argument
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
 __device__ __forceinline__ int fast_div(int x, unsigned m, int sh) {   // x / d for 0 <= x < 2^31 (host: igemm_fast_div)
     return m ? (int)(__umulhi((unsigned)x, m) >> sh) : x;
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // In-kernel phase timer (diagnostic builds only: -DTV_PROBE, tools/probes/igemm_phase_probe.py).  TV_T(i) adds the shader
@@ -182,9 +126,6 @@ __device__ __forceinline__ int swz_of(int i) {  // i: row index inside a 16-row 
 // every output is rounded to bf16 exactly once (a bf16 park rounded the pre-activation first: +20-40 % rel-L2 error on
 // whole-model outputs, tests/precision_report.py).
 // m_of_row(r) = output pixel index (b, oy, ox linearised) of wave-tile row r; the caller has synchronised the block.
-#ifndef TV_EPI_LDS
-#define TV_EPI_LDS 0   // 1: the round-1 epilogue (tile parked in LDS as fp32, streamed out row by row), kept for A/B timing
-#endif
 
 template <int WTM, int WTN>
 constexpr int epilogue_lds_bytes(int nwaves) {
@@ -357,15 +298,12 @@ __device__ __forceinline__ bf16x8 epi_math(float (&v)[8], const bf16x8& ld, cons
 // SH = store_shuffle of the launch (compile time): where element (GEMM row m, GEMM column nx .. nx+7) lives in the output
 // tensor -- the address arithmetic of the LDS loop, per 16-byte piece of a line (a 64-channel pair of blocks never straddles
 // a phase: the host sends only N/4 % 64 == 0 here).  Residual / saved tensors have the output's layout: same offsets.
-// TV_EPI_BUF (round 3): every load / store of the register epilogue goes through a buffer descriptor with a 32-bit byte offset
+// Round 3: every load / store of the register epilogue goes through a buffer descriptor with a 32-bit byte offset
 // per lane, masked pieces as OUT-OF-RANGE offsets (a store is dropped, a load returns zeros).  The pointer form predicated each
 // access (`if (ok) store`): one basic block and an s_cbranch_execz per store, 64-bit address arithmetic per piece -- the rows
 // of a tile went out strictly one after the other, every cross-lane transposition exposed in front of its store.  Without
 // branches the body is one block: the scheduler runs the transpositions of later rows under earlier stores.  The host sends
 // only tensors below 2 GiB here (out_bytes; larger ones keep the LDS loop).
-#ifndef TV_EPI_BUF
-#define TV_EPI_BUF 1
-#endif
 // Cache policy of the epilogue's stores (gfx950 aux bits: 1 sc0, 2 nt, 16 sc1).  Non-temporal: the output stream of a tile is written
 // once and not read by this launch -- kept out of the way of the operands the launch re-reads through L2 / the Infinity Cache:
 // linear layers -4...-7 % in isolation, bench +0.5-0.6 % (item 23; sc1: no change).  Chosen per launch (IgemmArgs.store_nt): an
@@ -374,9 +312,6 @@ __device__ __forceinline__ bf16x8 epi_math(float (&v)[8], const bf16x8& ld, cons
 #define TV_EPI_LOAD_AUX 0    // ... of the epilogue's residual / saved-derivative loads (read once)
 #endif
 typedef unsigned int epi_u32x4 __attribute__((__vector_size__(16)));
-#ifdef TV_EXP_GN_EPI
-__device__ float* g_gn_epi_buf = nullptr;   // timing experiment: per-wave GroupNorm partials [block][wave][256] (tv_set_gn_epi_probe)
-#endif
 __device__ __forceinline__ bf16x8 epi_bload(const void* base, unsigned bytes, int off) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const epi_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000), off, 0, TV_EPI_LOAD_AUX);
@@ -439,33 +374,13 @@ __device__ __forceinline__ void epilogue_direct(const IgemmArgs& p, const f32x4 
             }
         }
     };
-    // (the pointer form of an access, kept behind TV_EPI_BUF = 0 for A/B: same offsets, predicated)
     auto ld = [&](const bf16* base, int off) -> bf16x8 {
-#if TV_EPI_BUF
         return epi_bload(base, p.out_bytes, off);
-#else
-        return off != OOB_OFFSET ? *(const bf16x8*)((const char*)base + (unsigned)off) : zero8;
-#endif
     };
     auto st = [&](bf16* base, int off, const bf16x8& z) {
-#if TV_EPI_BUF
         if (p.store_nt) epi_bstore_nt(base, p.out_bytes, off, z);   // (wave-uniform)
         else epi_bstore(base, p.out_bytes, off, z);
-#else
-        if (off != OOB_OFFSET) *(bf16x8*)((char*)base + (unsigned)off) = z;
-#endif
     };
-#ifdef TV_EXP_GN_EPI
-    constexpr bool GNX = SH == 0 && (FORM == EF_PLAIN || FORM == EF_RES) && NC == 3;
-    [[maybe_unused]] float gs1[NC][8], gs2[NC][8];
-    [[maybe_unused]] const float gn_piv = p.bias ? p.bias[0] : 0.f;   // (stand-in pivot: a per-(image, channel) value in the real thing)
-    if constexpr (GNX) {
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) gs1[c][e] = gs2[c][e] = 0.f;
-    }
-#endif
     auto chunk_values = [&](int i, int c, float (&v)[8]) {
         const f32x4 lo = acc[i][2 * c] + bv[2 * c], hi = acc[i][2 * c + 1] + bv[2 * c + 1];
         v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3]; v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
@@ -476,7 +391,7 @@ __device__ __forceinline__ void epilogue_direct(const IgemmArgs& p, const f32x4 
         constexpr int P0 = ODD ? 1 : 0, NP = (NC - P0) / 2;
         constexpr int S0 = ODD ? 0 : NC - 1;             // the block without a partner, if any
         constexpr bool SINGLE = P0 + 2 * NP < NC || ODD;
-        static_for<0, MF / IB>([&](auto b_c) {
+        static_for<MF / IB>([&](auto b_c) {
             constexpr int i0 = decltype(b_c)::value * IB;
             int o1[IB][NP > 0 ? NP : 1], o2[IB][NP > 0 ? NP : 1], os[IB];
             [[maybe_unused]] bf16x8 la[IB][NP > 0 ? NP : 1], lb[IB][NP > 0 ? NP : 1], ls[IB];
@@ -540,16 +455,6 @@ __device__ __forceinline__ void epilogue_direct(const IgemmArgs& p, const f32x4 
                         st(p.pre, o1[ii][u], da);
                         st(p.pre, o2[ii][u], db);
                     }
-#ifdef TV_EXP_GN_EPI   // (timing experiment: GroupNorm statistics of the OUTPUT in the producing convolution's epilogue)
-                    if constexpr (GNX) {
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            const float xa = (float)za[e] - gn_piv, xb = (float)zb[e] - gn_piv;
-                            gs1[C0][e] += xa; gs2[C0][e] = fmaf(xa, xa, gs2[C0][e]);
-                            gs1[C0 + 1][e] += xb; gs2[C0 + 1][e] = fmaf(xb, xb, gs2[C0 + 1][e]);
-                        }
-                    }
-#endif
                     epi_to_lines(za, zb, lidx);
 #ifdef TV_ABL_NO_STORE
                     if (za[0] == (bf16)123.0f)   // (keeps the values live; practically never true)
@@ -581,15 +486,6 @@ __device__ __forceinline__ void epilogue_direct(const IgemmArgs& p, const f32x4 
                         epi_to_half(d, hidx);
                         st(p.pre, os[ii], d);
                     }
-#ifdef TV_EXP_GN_EPI
-                    if constexpr (GNX) {
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            const float xa = (float)z[e] - gn_piv;
-                            gs1[S0][e] += xa; gs2[S0][e] = fmaf(xa, xa, gs2[S0][e]);
-                        }
-                    }
-#endif
                     epi_to_half(z, hidx);
 #ifdef TV_ABL_NO_STORE
                     if (z[0] == (bf16)123.0f)
@@ -605,37 +501,6 @@ __device__ __forceinline__ void epilogue_direct(const IgemmArgs& p, const f32x4 
         if (nw0 & 32) run(std::true_type{});
         else run(std::false_type{});
     }
-#ifdef TV_EXP_GN_EPI
-    if constexpr (GNX) {
-        // the wave's 64 pixels per channel: the 16 lanes of a DPP row (same fq, pixels fi = 0..15) hold 48 partial values each
-        // (3 blocks x 8 channels x {sum, sum of squares}); reduce-scatter over the row in four halving steps (a lane keeps the
-        // half of the values its bit selects and adds the partner's copy of that half): 3 finished values per lane.
-        float v[48];
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { v[c * 16 + e] = gs1[c][e]; v[c * 16 + 8 + e] = gs2[c][e]; }
-        int n = 48;
-#pragma unroll
-        for (int bit = 8; bit >= 1; bit >>= 1) {
-            const bool up = (lane & bit) != 0;
-            const int h = n / 2;
-#pragma unroll
-            for (int k = 0; k < 24; ++k) {
-                if (k < h) {
-                    const float keep = up ? v[h + k] : v[k], send = up ? v[k] : v[h + k];
-                    v[k] = keep + __shfl_xor(send, bit, 64);
-                }
-            }
-            n = h;
-        }
-        // 3 values per lane; 64 lanes x 3 = the wave's 192 statistics -> its row of the partials buffer (16-byte aligned rows)
-        if (g_gn_epi_buf) {
-            float* dst = g_gn_epi_buf + ((size_t)blockIdx.x * 8 + (threadIdx.x >> 6)) * 256 + lane * 4;
-            *(f32x4*)dst = f32x4{v[0], v[1], v[2], 0.f};
-        }
-    }
-#endif
 }
 
 template <int WTM, int WTN, int EPI, class RowMap>
@@ -806,7 +671,7 @@ __device__ __forceinline__ void epilogue_lds(const IgemmArgs& p, const f32x4 (&a
 template <int WTM, int WTN, int EPI, bool REGFORMS, class RowMap>
 __device__ __forceinline__ void epilogue(const IgemmArgs& p, const f32x4 (&acc)[WTM / 16][WTN / 16], const f32x4 (&bv)[WTN / 16], char* smem,
                                          int wave, int lane, int nw0, RowMap m_of_row) {
-    constexpr bool REG = REGFORMS && !TV_EPI_LDS && (WTN / 16) % 2 == 0;
+    constexpr bool REG = REGFORMS && (WTN / 16) % 2 == 0;
     if constexpr (REG && EPI == 1) {
         epilogue_direct<WTM, WTN, EF_RES>(p, acc, bv, lane, nw0, m_of_row);
     } else if constexpr (REG && EPI == 2) {

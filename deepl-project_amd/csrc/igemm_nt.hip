@@ -101,9 +101,8 @@ template <int BM, int BN, int WGM, int WGN, int BK, int STAGES, int MODE>
 constexpr bool igemm_persist_ok() {
     constexpr int MF = BM / WGM / 16, NF = BN / WGN / 16, NW = WGM * WGN;
     constexpr bool pipe_all = (MF + NF) * 4 * (BK / 32) <= TV_PIPE_ALL_MAX;
-    constexpr bool pingpong = MODE != 0 && STAGES == 2 && NW == 8 && pipe_all && !TV_NO_PINGPONG;
-    constexpr bool pipe2 = MODE != 0 && pipe_all && BK == 64 && !pingpong && !TV_NO_PIPE2;
-    return MODE == 2 && STAGES == 2 && !pipe2 && !pingpong && BM * BN >= 128 * 128 && (NF % 2 == 0) && !TV_EPI_LDS && TV_GENERIC_BURST;
+    constexpr bool pipe2 = MODE != 0 && pipe_all && BK == 64;
+    return MODE == 2 && STAGES == 2 && !pipe2 && BM * BN >= 128 * 128 && (NF % 2 == 0);
 }
 // store instructions per wave of a register epilogue form on a full tile (epilogue_direct: per fragment row two per pair of
 // 32-channel blocks + one for a block without a partner; twice that where the derivative is saved as well)
@@ -395,10 +394,7 @@ __global__ __launch_bounds__(WGM* WGN * 64, (igemm_min_waves<BM, BN, WGM * WGN, 
     // of the K-step (both 32-deep halves) are issued up front, so the second half's ds_read_b128s fly under the first
     // half's MFMAs instead of exposing their latency a second time; the 256x256 tile keeps one half in flight at a time.
     constexpr bool PIPE_ALL = (MF + NF) * 4 * (BK / 32) <= TV_PIPE_ALL_MAX;
-    // `nbase` != nullptr: the DMA pieces of the K-step being staged go out between the MFMAs, one every GAP of them
-    constexpr int NMF = MF * NF * (BK / 32), GAP = NMF / NI > 0 ? NMF / NI : 1;
-    auto compute = [&](const char* sbase, char* nbase, auto issue_c) {
-        constexpr bool ISSUE = DMA && decltype(issue_c)::value;
+    auto compute = [&](const char* sbase) {
         if constexpr (PIPE_ALL) {
             bf16x8 af[BK / 32][MF], bfr[BK / 32][NF];
 #pragma unroll
@@ -428,18 +424,7 @@ __global__ __launch_bounds__(WGM* WGN * 64, (igemm_min_waves<BM, BN, WGM * WGN, 
 #else
                         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[kk][j], af[kk][i], acc[i][j], 0, 0, 0);
 #endif
-                        const int idx = (kk * MF + i) * NF + j;
-                        if (ISSUE && idx % GAP == GAP - 1 && idx / GAP < NI) {
-                            __builtin_amdgcn_sched_barrier(0);
-                            issue_piece(nbase, idx / GAP);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
                     }
-            if constexpr (ISSUE) {
-#pragma unroll
-                for (int q = NMF / GAP; q < NI; ++q) issue_piece(nbase, q);
-                stage_advance();
-            }
         } else {
 #pragma unroll
             for (int kk = 0; kk < BK / 32; ++kk) {
@@ -465,34 +450,18 @@ __global__ __launch_bounds__(WGM* WGN * 64, (igemm_min_waves<BM, BN, WGM * WGN, 
 #else
                         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
 #endif
-                        const int idx = (kk * MF + i) * NF + j;
-                        if (ISSUE && idx % GAP == GAP - 1 && idx / GAP < NI) {
-                            __builtin_amdgcn_sched_barrier(0);
-                            issue_piece(nbase, idx / GAP);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
                     }
-            }
-            if constexpr (ISSUE) {
-#pragma unroll
-                for (int qq = NMF / GAP; qq < NI; ++qq) issue_piece(nbase, qq);
-                stage_advance();
             }
         }
     };
 
     // ---- main loop -------------------------------------------------------------------------
-    // 8-wave tiles: waves w and w+4 share a SIMD.  With one barrier per K-step all eight issue their fragment reads
-    // together and every MFMA pipe idles until the LDS has served them (ablation: the reads cost 0.25-0.4 ms of 2.7).
-    // Ping-pong instead: the block runs in HALF-steps, group 0 (waves 0-3) reads the fragments of step t while group 1
-    // multiplies step t-1, then they swap, so each SIMD always has one wave in its MFMA phase.
-    constexpr bool PINGPONG = DMA && STAGES == 2 && NW == 8 && PIPE_ALL && !TV_NO_PINGPONG;
     // Register-pipelined loop (in-kernel timers: after a K-step barrier all waves read their fragments at once, ~640 LDS
     // cycles during which no MFMA issues).  Each wave keeps two half-step fragment sets: while the MFMAs of one half run,
     // the reads of the next half are in flight, ACROSS the stage boundary.  The block barrier therefore sits in the middle
     // of a K-step: every wave has read all of stage t (second half issued before the first half's MFMAs), stage t+1 has
     // landed, and stage t's buffer is refilled with stage t+STAGES between the MFMAs that follow.
-    constexpr bool PIPE2 = DMA && PIPE_ALL && BK == 64 && !PINGPONG && !TV_NO_PIPE2;
+    constexpr bool PIPE2 = DMA && PIPE_ALL && BK == 64;
     if constexpr (P8) {
         // ---- eight-phase wave-group ping-pong (round 3; the 256 x 256 tile on single-tap layers) ------------------------------
         // Ablation of the plain loop on K = 1536 -> N = 6144 (profiles/r03_kernel_experiments.txt item 13): 0.351 ms, without the
@@ -568,7 +537,7 @@ __global__ __launch_bounds__(WGM* WGN * 64, (igemm_min_waves<BM, BN, WGM * WGN, 
                 if (b == 1 || q < QB0) buffer_load_lds16(p.w, p.w_bytes, sb + bq_lds[b][q], bq_voff[b][q], t * (BK * 2));
         };
         // Fragment registers: one A half at a time; B0 stays resident for its two quadrants (phases 1 and 4) and B0 of the NEXT
-        // K-step is read in phase 4 into a second set (TV_P8_B0PF; balances the load sections: 8 / 4 / 8 / 4 reads on the
+        // K-step is read in phase 4 into a second set (balances the load sections: 8 / 4 / 8 / 4 reads on the
         // 256 x 256 tile instead of 12 / 4 / 8 / 4): for that the wait that retires step t+1 sits in L3 -- behind B0 of step
         // t+1 come only A0 and B1 of step t+2 then: vmcnt(4) -- and L4 reads two barriers later.
         bf16x8 fa[2][MH], fb0[2][2][NB0], fb1[2][NB1];
@@ -631,22 +600,16 @@ __global__ __launch_bounds__(WGM* WGN * 64, (igemm_min_waves<BM, BN, WGM * WGN, 
         if (nk > 1) { issue_A(1, 0); issue_B(1, 1); issue_A(1, 1); wait_vmcnt<6>(); }
         else wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();               // step 0 has landed for every wave
-#if TV_P8_B0PF
         read_B0(smem, I0{});                        // B0 of step 0 (its region is re-staged in L1 of step 1 at the earliest)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
         if (grp == 1) __builtin_amdgcn_s_barrier(); // group 1 runs one barrier behind
         // one K-step with B0 in register set S (the next step's goes to set 1 - S)
         auto kstep = [&](int t, auto set_c) {
             constexpr int S = decltype(set_c)::value;
-            using SC = std::integral_constant<int, TV_P8_B0PF ? S : 0>;
-            using SN = std::integral_constant<int, TV_P8_B0PF ? 1 - S : 0>;
+            using SC = std::integral_constant<int, S>;
+            using SN = std::integral_constant<int, 1 - S>;
             const char* sb = smem + (t & 1) * STAGE;
             // phase 1: quadrant (0, 0)
-#if !TV_P8_B0PF
-            read_B0(sb, SC{});
-            __builtin_amdgcn_sched_barrier(0);
-#endif
             read_A(sb, I0{});
             __builtin_amdgcn_sched_barrier(0);
             if (t + 1 < nk) issue_B(t + 1, 0);
@@ -662,23 +625,14 @@ __global__ __launch_bounds__(WGM* WGN * 64, (igemm_min_waves<BM, BN, WGM * WGN, 
             read_A(sb, I1{});
             __builtin_amdgcn_sched_barrier(0);
             if (t + 2 < nk) issue_B(t + 2, 1);
-#if TV_P8_B0PF
             if (t + 2 < nk) wait_vmcnt<4>();         // behind B0 of step t+1: A0, B1 of step t+2 -> step t+1 has landed
             else if (t + 1 < nk) wait_vmcnt<0>();
-#endif
             close_load();
             mfma_q(I1{}, I1{}, SC{});
             // phase 4: quadrant (1, 0)
-#if TV_P8_B0PF
             if (t + 1 < nk) read_B0(smem + ((t + 1) & 1) * STAGE, SN{});   // next step's B0: two barriers behind every wave's wait
             __builtin_amdgcn_sched_barrier(0);
             if (t + 2 < nk) issue_A(t + 2, 1);
-#else
-            read_B0(sb, SC{});
-            __builtin_amdgcn_sched_barrier(0);
-            if (t + 2 < nk) { issue_A(t + 2, 1); wait_vmcnt<6>(); }   // B0 of step t+1 and everything older has landed
-            else if (t + 1 < nk) wait_vmcnt<0>();
-#endif
             close_load();
             mfma_q(I1{}, I0{}, SC{});
         };
@@ -705,7 +659,7 @@ __global__ __launch_bounds__(WGM* WGN * 64, (igemm_min_waves<BM, BN, WGM * WGN, 
 #pragma unroll
                 for (int j = 0; j < NF; ++j) {
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
-                    const int idx = i * NF + j;   // DMA slots staggered by wave (see conv3x3_halo_kernel)
+                    const int idx = i * NF + j;   // DMA slots staggered by wave (dphase), so the eight waves do not queue at the address pipe at one MFMA index
                     if (ISSUE && idx / HGAP < NI && (TV_GENERIC_DPHASE ? idx % HGAP == dphase : idx % HGAP == HGAP - 1)) {
                         __builtin_amdgcn_sched_barrier(0);
                         issue_piece(nbase, idx / HGAP);
@@ -723,7 +677,7 @@ __global__ __launch_bounds__(WGM* WGN * 64, (igemm_min_waves<BM, BN, WGM * WGN, 
             if (s < nk) stage_issue(smem + s * STAGE);
         if (nk >= STAGES) wait_vmcnt<(STAGES - 1) * NI>();   // stage 0 landed
         else wait_vmcnt<0>();
-        if (TV_SETPRIO && NW == 8 && wave >= 4) __builtin_amdgcn_s_setprio(1);
+        if (NW == 8 && wave >= 4) __builtin_amdgcn_s_setprio(1);   // waves 4-7 (the arbitration losers on every SIMD) run at priority 1
         __builtin_amdgcn_s_barrier();
         read_half(smem, 0, f0a, f0b);
         int cur = 0, t = 0;
@@ -750,48 +704,6 @@ __global__ __launch_bounds__(WGM* WGN * 64, (igemm_min_waves<BM, BN, WGM * WGN, 
         for (; t + STAGES < nk; ++t) step(std::true_type{}, std::false_type{});
         for (; t + 1 < nk; ++t) step(std::false_type{}, std::false_type{});
         step(std::false_type{}, std::true_type{});
-    } else if constexpr (PINGPONG) {
-        // Both groups run the same code, group 1 one barrier behind.  Phase k lies between block barriers k and k+1:
-        //   group 0: reads step t in phase 2t,   multiplies it in phase 2t+1
-        //   group 1: reads step t in phase 2t+1, multiplies it in phase 2t+2
-        // The buffer of step t+1 is last read in phase 2t-1 and first read in phase 2t+2: every wave issues its share of
-        // that DMA in phase 2t and waits for it at the end of phase 2t+1.
-        const int grp = wave >> 2;
-        stage_issue(smem);
-        wait_vmcnt<0>();
-        if (grp == 1) {
-            __builtin_amdgcn_s_barrier();
-            if (1 < nk) stage_issue(smem + STAGE);
-        }
-        for (int t = 0; t < nk; ++t) {
-            __builtin_amdgcn_s_barrier();
-            if (grp == 0 && t + 1 < nk) stage_issue(smem + ((t + 1) & 1) * STAGE);
-            const char* sbase = smem + (t & 1) * STAGE;
-            bf16x8 af[BK / 32][MF], bfr[BK / 32][NF];
-#pragma unroll
-            for (int kk = 0; kk < BK / 32; ++kk) {
-                const int coff = ((kk * 4 + fq) ^ sw) * 16;
-#pragma unroll
-                for (int i = 0; i < MF; ++i) af[kk][i] = *(const bf16x8*)(sbase + a_row_off + i * 16 * (BK * 2) + coff);
-#pragma unroll
-                for (int j = 0; j < NF; ++j) bfr[kk][j] = *(const bf16x8*)(sbase + b_row_off + bfrag_off(j) * (BK * 2) + coff);
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the buffer may be refilled after the next barrier
-            if (grp == 1) wait_vmcnt<0>();
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_barrier();
-            if (grp == 1 && t + 2 < nk) stage_issue(smem + (t & 1) * STAGE);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int kk = 0; kk < BK / 32; ++kk)
-#pragma unroll
-                for (int i = 0; i < MF; ++i)
-#pragma unroll
-                    for (int j = 0; j < NF; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[kk][j], af[kk][i], acc[i][j], 0, 0, 0);
-            if (grp == 0) wait_vmcnt<0>();
-        }
-        if (grp == 0) __builtin_amdgcn_s_barrier();
     } else if constexpr (DMA && PERSIST) {
         // one K-loop over the block's ntile column tiles (STAGES == 2, burst issue): step g stages step g + 1, whichever tile
         // that belongs to; a tile's epilogue follows its last step
@@ -817,7 +729,7 @@ __global__ __launch_bounds__(WGM* WGN * 64, (igemm_min_waves<BM, BN, WGM * WGN, 
             __builtin_amdgcn_s_barrier();
             TV_T(1);
             if (g + 1 < total) stage_issue(smem + (cur ^ 1) * STAGE);
-            compute(smem + cur * STAGE, nullptr, std::false_type{});
+            compute(smem + cur * STAGE);
             TV_T(4);
             cur ^= 1;
             if (++t == nk) {   // the tile is complete
@@ -864,18 +776,12 @@ __global__ __launch_bounds__(WGM* WGN * 64, (igemm_min_waves<BM, BN, WGM * WGN, 
             __builtin_amdgcn_s_barrier();
 #endif
             TV_T(1);
-#if TV_GENERIC_BURST
 #ifdef TV_ABL_NO_DMA
             stage_advance();
 #else
             stage_issue(smem + nxt * STAGE);
 #endif
-            compute(smem + cur * STAGE, nullptr, std::false_type{});
-#elif !defined(TV_ABL_NO_DMA)
-            compute(smem + cur * STAGE, smem + nxt * STAGE, std::true_type{});
-#else
-            compute(smem + cur * STAGE, nullptr, std::false_type{});
-#endif
+            compute(smem + cur * STAGE);
             TV_T(4);
             cur = (cur + 1 == STAGES) ? 0 : cur + 1;
             nxt = (nxt + 1 == STAGES) ? 0 : nxt + 1;
@@ -888,7 +794,7 @@ __global__ __launch_bounds__(WGM* WGN * 64, (igemm_min_waves<BM, BN, WGM * WGN, 
             __builtin_amdgcn_s_barrier();
 #endif
             TV_T(1);
-            compute(smem + cur * STAGE, nullptr, std::false_type{});
+            compute(smem + cur * STAGE);
             TV_T(4);
             cur = (cur + 1 == STAGES) ? 0 : cur + 1;
         }
@@ -898,13 +804,13 @@ __global__ __launch_bounds__(WGM* WGN * 64, (igemm_min_waves<BM, BN, WGM * WGN, 
         for (int t = 0; t < nk; ++t) {
             __syncthreads();
             if (t + 1 < nk) stage_issue(nullptr);
-            compute(smem + (t & 1) * STAGE, nullptr, std::false_type{});
+            compute(smem + (t & 1) * STAGE);
             if (t + 1 < nk) stage_write(smem + ((t + 1) & 1) * STAGE);
         }
     }
 
     // ---- epilogue ---------------------------------------------------------------------------------
-    if (TV_SETPRIO) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
     TV_T(5);
 #ifdef TV_ABL_NO_EPI
     {
@@ -932,10 +838,6 @@ int g_cfg_stages = 0;  // 0 = heuristic, else 2 / 3 / 4
 int g_cfg_bk = 0;      // 0 = largest that divides c_in, else 32 / 64
 int g_addr_mode = 0;   // 0 = buffer DMA when the tensors are < 2 GiB, 1 = force 64-bit global DMA
 bool g_use_halo = true;  // 3x3 stride-1 convolutions through conv3x3_halo_kernel when the shape qualifies
-
-
-
-
 
 // register form of an EPI 0 launch (see epilogue<>): the common elementwise combinations; everything else -> LDS loop
 int epilogue_form(const IgemmArgs& a) {
@@ -1096,8 +998,6 @@ int launch_big(const IgemmArgs& a, int bm, int stages, hipStream_t s) {
         return launch_one<128, BN, 2, 2, BK, 2, MODE>(a, s);
     }
 }
-
-
 
 template <int BK, int MODE>
 int launch_mode(IgemmArgs& a, hipStream_t s) {

@@ -66,11 +66,6 @@ __global__ __launch_bounds__(256) void probe_rows_kernel(const float* __restrict
     }
 }
 
-__device__ __forceinline__ float sx_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ int sx_wave_sum(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -153,8 +148,8 @@ __global__ __launch_bounds__(SX_THREADS) void softmax_xent_kernel(const bf16* __
                 }
             }
         }
-        s = sx_wave_sum(s);
-        q = sx_wave_sum(q);
+        s = tv_wave_sum(s);
+        q = tv_wave_sum(q);
         acc[0] += (double)logf(s) + (1.0 - (double)eps) * (double)(m - xy) + ((double)eps / (double)n) * (double)q;
         acc[1] += 1.0;
         acc[2] += rank == 0 ? 1.0 : 0.0;

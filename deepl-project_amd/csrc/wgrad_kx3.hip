@@ -63,30 +63,9 @@ __device__ __forceinline__ int kx_swz(int c, int r) {
     }
 }
 
-template <int OFF>
-__device__ __forceinline__ bf16x4 lds_tr16(unsigned addr) {
-    static_assert(OFF >= 0 && OFF < 65536, "ds offset field is 16 bits");
-    bf16x4 r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
-    return r;
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 constexpr int kx_seg_stride(int seg) { return (seg + 2 + 7) / 8 * 8; }                 // tile rows per segment: 24 / 40 / 72
 constexpr int kx_x_pieces(int seg, int cx) { return ((64 / seg) * kx_seg_stride(seg) * cx + 63) / 64; }   // 1 KiB pieces of the x tile
 constexpr int kx_stage_bytes(int tg, int tx, int seg) { return 64 * tg * 2 + kx_x_pieces(seg, tx / 8) * 1024; }
-
-template <class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 // Schedule variants (VAR), all bit-identical in their results:
 //   0  every fragment read and every LDS-DMA piece in the load phase, K-step t + RING - 1 issued during step t
@@ -276,14 +255,14 @@ __global__ __launch_bounds__(512, 1) void wgrad_kx3_kernel(const Kx3Args p) {
             constexpr int i = R / 2, h = R % 2;
             constexpr int OFF = ((A_TWO && SLOT >= 2) ? (SLOT - 2) * G_BYTES : SLOT * G_BYTES) + KK * 32 * TG * 2 + h * 16 * TG * 2;
             const unsigned ab = (A_TWO && SLOT >= 2) ? a_base2[i] : a_base[i];
-            if constexpr (h == 0) alo[KK][i] = lds_tr16<OFF>(ab);
-            else ahi[KK][i] = lds_tr16<OFF>(ab);
+            if constexpr (h == 0) alo[KK][i] = lds_tr16_imm<OFF>(ab);
+            else ahi[KK][i] = lds_tr16_imm<OFF>(ab);
         } else {
             constexpr int rr = R - 2 * MF, tp = rr / (2 * NF), j = (rr / 2) % NF, h = rr % 2;
             constexpr int OFF = ((B_TWO && SLOT >= 2) ? (SLOT - 2) * X_BYTES : SLOT * X_BYTES) + KK * KK_ROWS * TX * 2 + h * H_ROWS * TX * 2;
             const unsigned bb = (B_TWO && SLOT >= 2) ? b_base2[tp][j] : b_base[tp][j];
-            if constexpr (h == 0) blo[KK][tp][j] = lds_tr16<OFF>(bb);
-            else bhi[KK][tp][j] = lds_tr16<OFF>(bb);
+            if constexpr (h == 0) blo[KK][tp][j] = lds_tr16_imm<OFF>(bb);
+            else bhi[KK][tp][j] = lds_tr16_imm<OFF>(bb);
         }
     };
     auto mfma_one = [&](auto kk_c, auto m_c) {
@@ -308,7 +287,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_kx3_kernel(const Kx3Args p) {
 #pragma unroll
     for (int st = 0; st < LOOK; ++st)
         if (st < nsteps) stage_issue(st, st);
-    wait_vm<0>();
+    wait_vmcnt<0>();
     if (grp == 1) __builtin_amdgcn_s_barrier();
 
     // one K-step with the ring slot as a compile-time constant
@@ -343,9 +322,9 @@ __global__ __launch_bounds__(512, 1) void wgrad_kx3_kernel(const Kx3Args p) {
             constexpr int NLX = IT_SPLIT > G_IT ? IT_SPLIT - G_IT : 0;                  // x piece iterations issued in a load phase
             constexpr int P_HI = G_IT + X_IT, P_LO = G_IT + X_IT - (XR != 0 ? 1 : 0);   // pieces per step: waves below XR / the others
             constexpr int L_HI = NLG + NLX, L_LO = NLG + NLX - ((XR != 0 && NLX == X_IT) ? 1 : 0);
-            if (!more) wait_vm<0>();
-            else if (XR != 0 && wave < XR) wait_vm<(LOOK - 2) * P_HI + L_HI>();
-            else wait_vm<(LOOK - 2) * P_LO + L_LO>();
+            if (!more) wait_vmcnt<0>();
+            else if (XR != 0 && wave < XR) wait_vmcnt<(LOOK - 2) * P_HI + L_HI>();
+            else wait_vmcnt<(LOOK - 2) * P_LO + L_LO>();
         }
         // ---- MFMA phase ----------------------------------------------------------------------------------------------------
         __builtin_amdgcn_s_barrier();

@@ -53,10 +53,6 @@ __device__ __forceinline__ int tn_swz(int c, int r) {
     }
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 // wait until at most `younger` K-steps (NI DMA instructions each) are still in flight
 template <int NI, int K>
 struct WaitSel {
@@ -69,20 +65,6 @@ template <int NI>
 struct WaitSel<NI, 0> {
     static __device__ __forceinline__ void run(int) { wait_vmcnt<0>(); }
 };
-
-// ds_read_b64_tr_b16 through inline asm: with the builtin, hipcc (ROCm 7.2) puts an s_waitcnt vmcnt(0) in
-// front of every transposed read while an LDS-DMA is in flight (it does not for plain ds_read_b128), which
-// drains the ring each K-step.  An asm read is invisible to that pass; its completion is waited for by the
-// explicit lgkmcnt(0) + sched_barrier pairs below (cdna_hip_programming.md section 5.7, rule 18).
-__device__ __forceinline__ bf16x4 lds_tr16(unsigned lds_addr) {
-    bf16x4 r;
-    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(r) : "v"(lds_addr) : "memory");
-    return r;
-}
-__device__ __forceinline__ void lds_wait_all() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
 
 // BKP = pixels per K-step (32 or 64): 64 halves the barriers / index arithmetic per MFMA
 // min waves/SIMD asked of the register allocator: 3 blocks/CU for the 4-wave tiles with <= 16 accumulator
@@ -284,14 +266,9 @@ __global__ __launch_bounds__(128 * NWN, (wgrad_min_waves<TG, TX, NWN>())) void w
     //  tiles_ci blocks of a pixel chunk that share a co tile hold the same gy fragments, so they take the K-steps in turn.
     //  Every block therefore ADDS its share into dbias with atomics, single-chunk launches included: the caller passes a
     //  zeroed dbias, or one that holds a running sum.)
-#ifdef TV_BIAS_ONE_OWNER      // (A/B build: the round-2 scheme)
-    const bool one_owner = true;
-#else
-    const bool one_owner = false;
-#endif
-    const bool do_bias = (p.dbias != nullptr) && (!one_owner || (ci_tile == 0 && tap == 0));
-    const int nshare = one_owner ? 1 : taps * p.tiles_ci;
-    int bias_ctr = one_owner ? 0 : tap * p.tiles_ci + ci_tile;     // K-steps until this block's next turn
+    const bool do_bias = p.dbias != nullptr;
+    const int nshare = taps * p.tiles_ci;
+    int bias_ctr = tap * p.tiles_ci + ci_tile;     // K-steps until this block's next turn
     bool bias_now = false;
     auto bias_turn = [&]() {     // call once per K-step, before its fragments are summed
         bias_now = do_bias && bias_ctr == 0;

@@ -32,6 +32,25 @@ def test_activation_ids_agree():
     assert pub["TV_ACT_SAVE_DERIV"] & (pub["TV_ACT_GELU"] | pub["TV_ACT_SILU"] | pub["TV_ACT_DERIV"]) == 0
 
 
+def test_compile_time_switches_are_documented():
+    """Every `#ifndef TV_X` block in csrc/ that defines TV_X (a default a build may override) has a line in the first table of DESIGN.md's section
+    "Compile-time switches", and the table names nothing else: a switch cannot appear (or go) without saying what it is for."""
+    import glob
+    csrc = os.path.join(ROOT, "deepl-project_amd", "csrc")
+    guarded = set()
+    for path in glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")):
+        # (`#ifndef TV_X` as a plain condition, e.g. around a barrier that an ablation define takes out, defines nothing)
+        guarded |= set(re.findall(r"^[ \t]*#[ \t]*ifndef[ \t]+(TV_\w+)\b(?:(?!^[ \t]*#[ \t]*endif).)*?^[ \t]*#[ \t]*define[ \t]+\1\b",
+                                  open(path).read(), flags=re.M | re.S))
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = re.split(r"^#+ .*Compile-time switches.*$", design, maxsplit=1, flags=re.M)
+    assert len(section) == 2, "DESIGN.md has no section 'Compile-time switches'"
+    table = re.search(r"(?:^\|.*\n)+", section[1], flags=re.M).group(0).splitlines()   # the first table of the section
+    named = [re.match(r"\|\s*`(TV_\w+)`", row).group(1) for row in table[2:]]           # (header and separator rows skipped)
+    assert len(named) == len(set(named)), sorted(n for n in named if named.count(n) > 1)
+    assert guarded and set(named) == guarded, (sorted(guarded - set(named)), sorted(set(named) - guarded))
+
+
 def test_library_loads_and_exports_every_symbol():
     from transvae.hip import _lib
     _lib.build()

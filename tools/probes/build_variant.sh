@@ -1,6 +1,7 @@
 #!/bin/bash
 # Builds a variant of the library with extra -D flags on ONE source file (the other objects come from the in-tree build):
-#   tools/probes/build_variant.sh pp igemm_nt.hip -DTV_HALO_PP=1      ->  tools/probes/abl/lib_pp.so
+#   tools/probes/build_variant.sh ns4 attention.hip -DTV_ATTN_NS=4    ->  tools/probes/abl/lib_ns4.so
+# (the switches and constants a variant can set: DESIGN.md, "Compile-time switches")
 set -e
 name=$1; src=$2; shift 2
 cd "$(dirname "$0")/../../deepl-project_amd"
