@@ -5,7 +5,9 @@ of x over 2^-6..2^6, bias / residual that match or dominate the accumulator, rag
 attention with a large common offset on v, spiked keys and rows whose max grows across the lazy-rescale threshold;
 GroupNorm with |mean| up to 100 std; the production attention branch (fused.AttnBranchFn): rms_ln_hat with |mean u| up to
 100 std u and the fused residual gradient, RoPE in the QKV projection's epilogue across image boundaries, the RoPE adjoint
-in the attention-backward stores.  Every tuning hook a test sets is restored in a `finally`.
+in the attention-backward stores; the production GroupNorm + SiLU path (fused.gn_silu_fwd / gn_silu_apply / gn_silu_bwd with
+the fused skip-connection gradient) over its thread geometries, at outlier pivots and on its non-temporal instantiations.
+Every tuning hook a test sets is restored in a `finally`.
 """
 import pytest
 import torch
@@ -15,8 +17,8 @@ import functools
 from test_error_budget_host import (
     BF, EPS_LN, EPS_RMS, F64, LSE_C, ROWNORM_C_DW, WGRAD_C, act_grad64, attn_bwd_emul, attn_bwd_exact, attn_exact,
     attn_fwd_emul, attn_inputs, check_fp32, check_one_rounding, check_vs_emulation, conv64, deriv64, epilogue64, f32,
-    gemm_inputs, gn_inputs, gn_silu64, lse_terms, r16, rms_ln_hat64, rms_ln_inputs, rms_ln_slack, rope_epilogue64,
-    rownorm_bwd64, rownorm_dres, wgrad64)
+    gemm_inputs, gn_bwd64, gn_case, gn_check_all, gn_inputs, gn_k_g, gn_silu64, check_gn_stats, lse_terms, r16,
+    rms_ln_hat64, rms_ln_inputs, rms_ln_slack, rope_epilogue64, rownorm_bwd64, rownorm_dres, ulp16, wgrad64)
 
 pytestmark = pytest.mark.gpu
 
@@ -460,27 +462,217 @@ def test_groupnorm_silu(B, HW, C, G):
     y = ops.group_norm_silu(xd, gd, bd, G)
     y.backward(gy.view(B, H, HW // H, C).to(dev(), BF))
     torch.cuda.synchronize()
-    y64, slack, z, xh, rstd = gn_silu64(x, gamma, beta, G)
+    y64, slack, *_ = gn_silu64(x, gamma, beta, G)
     out = {"y": check_one_rounding(y.cpu().view(B, HW, C), y64, slack, "GroupNorm + SiLU forward")}
-    # backward in fp64: g' = gy silu'(z); dx = rstd gamma (g' - mean g' - xhat mean(g' xhat)) per group
-    gp = gy * act_grad64(z, "silu")
-    gpg = (gp * gamma).view(B, HW, G, C // G)
-    xhg = xh.view(B, HW, G, C // G)
-    r = rstd.view(B, 1, G, 1)
-    m1 = gpg.mean((1, 3), keepdim=True)
-    m2 = (gpg * xhg).mean((1, 3), keepdim=True)
-    dx64 = (r * (gpg - m1 - xhg * m2)).view(B, HW, C)
-    mu_r = (x.view(B, HW, G, C // G).mean((1, 3), keepdim=True) * r).abs()
-    # fp32 z (2^-22 (|x sc| + |sh|)) moves silu'; the sums and the final fma chain: 2^-19 of the terms' magnitudes
-    terms = (r * (gpg.abs() + gpg.abs().mean((1, 3), keepdim=True) + xhg.abs() * (gpg * xhg).abs().mean((1, 3), keepdim=True))).view(B, HW, C)
-    dsl = 2.0 ** -19 * terms * (1 + mu_r.expand(B, HW, G, C // G).reshape(B, HW, C)) + 2.0 ** -20 * dx64.abs()
+    dx64, dsl, dg64, db64, pterms = gn_bwd64(x, gamma, beta, gy, None, G)      # the fp64 backward and its slacks
     out["dx"] = check_one_rounding(xd.grad.cpu().view(B, HW, C), dx64, dsl, "GroupNorm + SiLU dx")
-    dg64 = (gp * xh).sum((0, 1))
-    db64 = gp.sum((0, 1))
-    xh_err = (mu_r.expand(B, HW, G, C // G).reshape(B, HW, C) + xh.abs() + 1)   # xhat to 2^-22 of |x| rstd
-    out["dgamma"] = (check_fp32(gd.grad.cpu(), dg64, (gp.abs() * xh_err).sum((0, 1)), 64.0, "dgamma"),)
-    out["dbeta"] = (check_fp32(bd.grad.cpu(), db64, (gp.abs() * xh_err).sum((0, 1)), 64.0, "dbeta"),)
+    out["dgamma"] = (check_fp32(gd.grad.cpu(), dg64, pterms, 64.0, "dgamma"),)
+    out["dbeta"] = (check_fp32(bd.grad.cpu(), db64, pterms, 64.0, "dbeta"),)
     report(f"[N] GroupNorm {B}x{HW}x{C}/{G}", {k: tuple(round(v, 3) for v in t) for k, t in out.items()})
+
+
+# the production path: fused.gn_silu_fwd / gn_silu_apply / gn_silu_bwd, the calls of fused.ResBlockFn.
+# What the inputs make visible (norm.hip): dres added after the bf16 rounding -- rownorm_dres cancels dx on even pixels, so the
+# second rounding is taken at dx's magnitude and read at the sum's (the host mutation `dres_after`); a FROM_MR kernel whose sc
+# is not gn_prepare's expression -- the bit-equality of gn_silu_apply, plain and NT; a pixel loop without its `min(hw, ...)` --
+# every B > 1 case with hw % 512 != 0 pulls the next image's pixels into the statistics / the backward sums, and the guarded
+# buffers of test_groupnorm_stays_inside_a_ragged_last_slab show the stray stores; `(chunk * 8) / cpg` as a channel's group --
+# wrong statistics for part of every 8-vector unless cpg is a multiple of 8 (cpg = 1, 2, 6, 10, 12, 24 here).
+GN_PROD_CASES = [
+    # B, HW, C, G                thread geometry: nch = C / 8 threads per pixel, rows = 256 / nch pixel lanes, slabs of 512 pixels
+    (1, 1, 32, 32),            # cpg 1 (Chan's merge of one channel), a single pixel, var 0, 63 of 64 lanes without a pixel
+    (2, 3, 1536, 32),          # rows 1, 64 idle threads, hw < 512
+    (3, 513, 2048, 32),        # the C limit, a second slab of one pixel
+    (2, 512, 768, 32),         # exactly one slab
+    (3, 511, 320, 32),         # cpg 10, 16 idle threads
+    (2, 1537, 384, 32),        # a ragged fourth slab
+    (2, 4103, 192, 32),        # cpg 6: 8-vectors straddle groups; 9 slabs, 16 idle threads
+    (1, 65536, 64, 32),        # 128 partials through gn_finalize_kernel
+    (2, 700, 64, 1),           # one group for all channels
+    (2, 700, 64, 8),           # C / 8 groups: one per vector
+]
+
+
+def _gn_prod_run(x, gamma, beta, gy, dres_list, G, eps=1e-5):
+    """fused.gn_silu_fwd, gn_silu_apply and gn_silu_bwd once per entry of dres_list (None or a [B, HW, C] tensor) ->
+    (mr, y, y of the apply, [(dx, dgamma, dbeta), ...]) on the host"""
+    from transvae.hip import fused
+    B, HW, C = x.shape
+    up = lambda t: t.view(B, 1, HW, C).to(dev(), BF).contiguous()
+    xd, gyd = up(x), up(gy)
+    gd, bd = gamma.float().to(dev()), beta.float().to(dev())
+    y, mr = fused.gn_silu_fwd(xd, gd, bd, G, eps)
+    y2 = fused.gn_silu_apply(xd, mr, gd, bd, G)
+    outs = [fused.gn_silu_bwd(xd, gyd, None if dr is None else up(dr), mr, gd, bd, G) for dr in dres_list]
+    torch.cuda.synchronize()
+    return mr.cpu(), y.cpu().view(B, HW, C), y2.cpu().view(B, HW, C), [(a.cpu().view(B, HW, C), b.cpu(), c.cpu()) for a, b, c in outs]
+
+
+def _gn_prod_check(shape, k, tag):
+    """one production-path case at pivot offset k: every assertion of test_groupnorm_production_path -> the y error in ulps"""
+    B, HW, C, G = shape
+    case = gn_case(shape, k)
+    x, gamma, beta, gy, dres = case[:5]
+    mr, y, y2, runs = _gn_prod_run(x, gamma, beta, gy, [None, dres, torch.zeros_like(dres)], G)
+    mr_b, y_b, y2_b, runs_b = _gn_prod_run(x, gamma, beta, gy, [None], G)
+    assert bool(torch.isfinite(y.float()).all()) and all(bool(torch.isfinite(r[0].float()).all()) for r in runs)
+    out = gn_check_all(case, shape, dict(mr=mr, y=y, dx=runs[0][0], dgamma=runs[0][1], dbeta=runs[0][2]), dict(dx=runs[1][0]), tag, bias=(k == 0))
+    report(f"[N] production GroupNorm {tag} (ratio, max ulps, bias)", out)
+    assert torch.equal(y2, y), f"{tag}: gn_silu_apply differs from gn_silu_fwd in {int((y2 != y).sum())} elements"
+    assert torch.equal(runs[2][0], runs[0][0]), f"{tag}: an all-zero dres changes dx"
+    assert torch.equal(mr_b, mr) and torch.equal(y_b, y) and torch.equal(y2_b, y), f"{tag}: the forward is not bit-reproducible"
+    assert torch.equal(runs_b[0][0], runs[0][0]), f"{tag}: dx is not bit-reproducible"
+    y64 = case[5][0]
+    return ((y.to(F64) - y64).abs() / ulp16(y64)).max().item()
+
+
+@pytest.mark.parametrize("shape", GN_PROD_CASES, ids=lambda s: "x".join(map(str, s[:3])) + f"-G{s[3]}")
+def test_groupnorm_production_path(shape):
+    """[N] the three calls fused.ResBlockFn makes, over the thread geometries of GN_PROD_CASES: mean / rstd inside the bound
+    about the pivot; y one rounding; gn_silu_apply (the FROM_MR recompute) bit-equal to the forward's y; dx one rounding
+    without dres, with a dres of dx's own magnitude that partly cancels it (rownorm_dres) and bit-equal under an all-zero
+    dres; dgamma / dbeta fp32 sums at c = max(64, k_g); forward and dx bit-identical over two runs."""
+    _gn_prod_check(shape, 0, "x".join(map(str, shape)))
+
+
+@pytest.mark.parametrize("shape", [(2, 4096, 192, 32), (1, 65536, 64, 32)], ids=lambda s: "x".join(map(str, s[:3])))
+def test_groupnorm_pivot_outlier(shape):
+    """[N] pixel 0 of every channel -- the pivot of gn_stats_kernel -- 0, 8 and 64 group-sigma from the group mean: the sums
+    about it lose accuracy as dm^2 / var grows, which the bounds carry (gn_stats64).  Same assertions as the production-path
+    test (the rounding-bias figure is asserted at offset 0 only, see gn_check_all); the absolute y error in bf16 ulps is
+    printed per offset."""
+    for k in (0, 8, 64):
+        ulps = _gn_prod_check(shape, k, "x".join(map(str, shape)) + f" pivot +{k} sigma")
+        report(f"[N] GroupNorm {shape} pivot +{k} sigma, max |y - y64| in bf16 ulps", round(ulps, 3))
+
+
+def test_groupnorm_accumulates_parameter_gradients():
+    """[N] tv_gn_silu_bwd_apply ADDS into dgamma / dbeta (atomics): on top of a running sum N(0, 4) the result is the sum plus
+    the fp64 gradient within the fp32 bound, terms + |base| (the third run of test_rms_ln_hat)"""
+    import ctypes as C
+    from transvae.hip import _lib as L, fused
+    lib = L.load()
+    shape = (3, 511, 320, 32)
+    B, HW, Cc, G = shape
+    case = gn_case(shape, 0)
+    x, gamma, beta, gy, dres = case[:5]
+    dx64, dsl, dg64, db64, pterms = case[7]
+    g = torch.Generator().manual_seed(5)
+    base_g, base_b = f32(torch.randn(Cc, generator=g, dtype=F64) * 2), f32(torch.randn(Cc, generator=g, dtype=F64) * 2)
+    up = lambda t: t.view(B, 1, HW, Cc).to(dev(), BF).contiguous()
+    xd, gyd, rd = up(x), up(gy), up(dres)
+    gd, bd = gamma.float().to(dev()), beta.float().to(dev())
+    _, mr = fused.gn_silu_fwd(xd, gd, bd, G, 1e-5)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    red = torch.empty((B, Cc, 2), dtype=torch.float32, device=dev())
+    part = torch.empty((lib.tv_gn_partial_count(B, HW, Cc),), dtype=torch.float32, device=dev())
+    dx = torch.empty_like(xd)
+    dg, db = base_g.float().to(dev()).contiguous(), base_b.float().to(dev()).contiguous()
+    L.check(lib.tv_gn_silu_bwd_reduce(p(xd), p(gyd), p(mr), p(gd), p(bd), p(red), p(part), B, HW, Cc, G, stream), "tv_gn_silu_bwd_reduce")
+    L.check(lib.tv_gn_silu_bwd_apply(p(xd), p(gyd), p(rd), p(mr), p(red), p(gd), p(bd), p(dx), p(dg), p(db), B, HW, Cc, G, stream),
+            "tv_gn_silu_bwd_apply")
+    torch.cuda.synchronize()
+    c = max(64.0, gn_k_g(HW, Cc, B))
+    out = {"dx+dres": check_one_rounding(dx.cpu().view(B, HW, Cc), dx64, dsl, "dx + dres"),
+           "dgamma": (check_fp32(dg.cpu(), base_g + dg64, pterms + base_g.abs(), c, "dgamma on a running sum"),),
+           "dbeta": (check_fp32(db.cpu(), base_b + db64, pterms + base_b.abs(), c, "dbeta on a running sum"),)}
+    report(f"[N] GroupNorm {shape} parameter gradients on a running sum", {k: tuple(round(v, 4) for v in t) for k, t in out.items()})
+
+
+def test_groupnorm_nontemporal_instantiations_equal_the_plain_ones():
+    """[N] B = 2, HW = 65 536, C = 512 is exactly 128 MiB: every launch takes the NT = true kernels (norm.hip gn_nt), while each
+    image alone (64 MiB) takes the plain ones.  Images are independent and every reduction has a fixed order, so mr, y, the
+    apply's y and dx (+ dres) of the pair are bit-equal to the two single-image runs, and dgamma / dbeta of the pair to the sum
+    of the singles' (two addends from zero; addition commutes).  Everything stays on the device; the singles' mr is checked
+    against fp64 statistics in plain torch there."""
+    from transvae.hip import fused
+    B, HW, C, G = 2, 65536, 512, 32
+    assert B * HW * C * 2 == 128 << 20
+    g = torch.Generator(device=dev()).manual_seed(11)
+    rnd = lambda *s: torch.randn(*s, generator=g, device=dev(), dtype=torch.float32)
+    std = torch.exp2(4 * rnd(B, 1, G, 1))
+    x = ((rnd(B, HW, G, C // G) + 10 * rnd(B, 1, G, 1)) * std).view(B, 1, HW, C).to(BF).contiguous()
+    gy = rnd(B, 1, HW, C).to(BF)
+    dres = (rnd(B, 1, HW, C) / std.expand(B, HW, G, C // G).reshape(B, 1, HW, C)).to(BF)      # the magnitude of dx ~ gy rstd
+    gamma, beta = 1 + 0.2 * rnd(C), 0.2 * rnd(C)
+
+    def run(xs, gs, ds):
+        y, mr = fused.gn_silu_fwd(xs, gamma, beta, G, 1e-5)
+        y2 = fused.gn_silu_apply(xs, mr, gamma, beta, G)
+        dx, dg, db = fused.gn_silu_bwd(xs, gs, ds, mr, gamma, beta, G)
+        return mr, y, y2, dx, dg, db
+    pair = run(x, gy, dres)
+    singles = [run(x[b:b + 1], gy[b:b + 1], dres[b:b + 1]) for b in range(B)]
+    torch.cuda.synchronize()
+    assert torch.equal(pair[2], pair[1]), "NT apply differs from the NT forward"
+    for i, nm in enumerate(("mr", "y", "apply y", "dx + dres")):
+        for b in range(B):
+            assert x[b:b + 1].is_contiguous() and torch.equal(pair[i][b:b + 1], singles[b][i]), f"{nm} of image {b}: NT and plain kernels differ"
+    for i, nm in ((4, "dgamma"), (5, "dbeta")):
+        assert torch.equal(pair[i], singles[0][i] + singles[1][i]), f"{nm}: the pair is not the sum of the single images"
+    assert bool(torch.isfinite(pair[3].float()).all()) and float(pair[3].float().abs().max()) > 0
+    rat = [check_gn_stats(x[b].view(1, HW, C), G, singles[b][0], f"plain kernels, image {b}") for b in range(B)]
+    report(f"[N] NT = plain at {B}x{HW}x{C}; single-image (mean, rstd) ratios", [tuple(round(v, 4) for v in r) for r in rat])
+
+
+def test_groupnorm_stays_inside_a_ragged_last_slab():
+    """[N] hw = 513: the second slab holds one pixel.  The five entry points run through ctypes on buffers that continue for
+    511 more pixels -- inputs there hold large finite values, outputs a sentinel -- so a pixel loop that ran to the end of its
+    slab instead of to hw would stay inside the allocations, change the statistics and overwrite the sentinel.  The results
+    are bit-equal to the fused.* calls on the exact-size tensors and every sentinel is intact."""
+    import ctypes as C
+    from transvae.hip import _lib as L, fused
+    lib = L.load()
+    shape = (1, 513, 64, 32)
+    B, HW, Cc, G = shape
+    PAD = 1024
+    x, gamma, beta, gy, dres = gn_case(shape, 0)[:5]
+
+    def padded(t, fill):
+        buf = torch.full((PAD, Cc), fill, dtype=BF, device=dev())
+        if t is not None:
+            buf[:HW] = t.view(HW, Cc).to(dev(), BF)
+        return buf
+    xd, gyd, rd = padded(x, 3e4), padded(gy, 3e4), padded(dres, 3e4)
+    y, y2, dx = padded(None, 768.0), padded(None, 768.0), padded(None, 768.0)
+    gd, bd = gamma.float().to(dev()), beta.float().to(dev())
+    f32buf = lambda *s: torch.empty(s, dtype=torch.float32, device=dev())
+    stats, red, mr = f32buf(B, Cc, 2), f32buf(B, Cc, 2), f32buf(B, G, 2)
+    part = f32buf(lib.tv_gn_partial_count(B, HW, Cc))
+    dg, db = torch.zeros(Cc, device=dev()), torch.zeros(Cc, device=dev())
+    p = lambda t: C.c_void_p(t.data_ptr())
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    L.check(lib.tv_gn_stats(p(xd), p(stats), p(part), B, HW, Cc, stream), "tv_gn_stats")
+    L.check(lib.tv_gn_silu_fwd(p(xd), p(stats), p(gd), p(bd), p(mr), p(y), B, HW, Cc, G, 1e-5, stream), "tv_gn_silu_fwd")
+    L.check(lib.tv_gn_silu_apply(p(xd), p(mr), p(gd), p(bd), p(y2), B, HW, Cc, G, stream), "tv_gn_silu_apply")
+    L.check(lib.tv_gn_silu_bwd_reduce(p(xd), p(gyd), p(mr), p(gd), p(bd), p(red), p(part), B, HW, Cc, G, stream), "tv_gn_silu_bwd_reduce")
+    L.check(lib.tv_gn_silu_bwd_apply(p(xd), p(gyd), p(rd), p(mr), p(red), p(gd), p(bd), p(dx), p(dg), p(db), B, HW, Cc, G, stream),
+            "tv_gn_silu_bwd_apply")
+    xe, gye, re_ = (t[:HW].clone().view(B, 1, HW, Cc) for t in (xd, gyd, rd))
+    ye, mre = fused.gn_silu_fwd(xe, gd, bd, G, 1e-5)
+    dxe, dge, dbe = fused.gn_silu_bwd(xe, gye, re_, mre, gd, bd, G)
+    torch.cuda.synchronize()
+    for nm, buf in (("y", y), ("apply y", y2), ("dx", dx)):
+        assert bool((buf[HW:] == 768.0).all()), f"{nm}: stores past pixel hw - 1"
+    assert torch.equal(mr, mre), "statistics read pixels past hw - 1"
+    assert torch.equal(y[:HW], ye.view(HW, Cc)) and torch.equal(y2[:HW], ye.view(HW, Cc))
+    assert torch.equal(dx[:HW], dxe.view(HW, Cc)) and torch.equal(dg, dge) and torch.equal(db, dbe), "backward sums read pixels past hw - 1"
+
+
+@pytest.mark.parametrize("C,G", [(2056, 32), (36, 4), (64, 5)])
+def test_groupnorm_rejects_bad_shapes(C, G):
+    """[N] argument validation only: C > 2048 (more 8-vectors than threads), C % 8 != 0 and C % G != 0 raise through L.check
+    with gn_check's message from every entry point, before any launch"""
+    from transvae.hip import fused
+    x = torch.zeros(1, 2, 2, C, dtype=BF, device=dev())
+    w = torch.ones(C, dtype=torch.float32, device=dev())
+    mr = torch.zeros(1, G, 2, dtype=torch.float32, device=dev())
+    for call in (lambda: fused.gn_silu_fwd(x, w, w, G, 1e-5), lambda: fused.gn_silu_apply(x, mr, w, w, G),
+                 lambda: fused.gn_silu_bwd(x, x, None, mr, w, w, G)):
+        with pytest.raises(RuntimeError, match=rf"bad shape batch=1 hw=4 C={C} G=\d+ \(C % 8 == 0, C % G == 0, C <= 2048 required\)"):
+            call()
+    torch.cuda.synchronize()
 
 
 ROWNORM_LOOP = 8192 + 4 * 2048 + 13     # rows: the forward's 2048 blocks x 4 waves twice and a ragged third pass, the backward's

@@ -25,8 +25,14 @@ Checks
 The production attention branch (fused.AttnBranchFn) has its own references here: rms_ln_hat64 / rownorm_bwd64 ([N], mode 1
 and the fused residual gradient), rope_epilogue64 ([G], RoPE on the accumulator of the QKV projection) and the `tab` argument
 of attn_bwd_exact / attn_bwd_emul ([A], the RoPE adjoint in the dq / dk stores), each with its fp32 emulation and mutations.
+
+The production GroupNorm + SiLU path (fused.gn_silu_fwd / gn_silu_apply / gn_silu_bwd, the calls of fused.ResBlockFn):
+gn_stats64 (the mean / rstd bounds about the kernels' pivot, k_s), gn_silu64, gn_bwd64 (the fp64 backward with dres, k_g),
+gn_kernel_emul_ordered (fp32 in the kernels' own order of operations) and its eleven mutations.
 """
+import functools
 import math
+import re
 
 import numpy as np
 import pytest
@@ -344,6 +350,75 @@ def attn_bwd_emul(q, k, v, o, do, lse, scale, mutate=None, tab=None):
 # ---------------------------------------------------------------------------------------------------------------------------
 # norms in fp64
 # ---------------------------------------------------------------------------------------------------------------------------
+GN_THREADS, GN_SLAB = 256, 512      # norm.hip: GN_THREADS, GN_PIX_PER_BLOCK
+U32 = 2.0 ** -24                     # unit roundoff of fp32
+
+
+def gn_rows(C):
+    """pixel lanes of a GroupNorm block: nch = C / 8 threads cover one pixel, rows = 256 / nch pixels per sweep"""
+    return GN_THREADS // (C // 8)
+
+
+def gn_chain(hw, C):
+    """additions behind one per-channel sum of the GroupNorm kernels: a lane's chain over its pixels of a slab, the lanes in
+    order through LDS, the slabs in order (gn_finalize_kernel)"""
+    rows = gn_rows(C)
+    return -(-min(hw, GN_SLAB) // rows) + rows + -(-hw // GN_SLAB)
+
+
+def gn_k_s(hw, C, G):
+    """[N] additions behind a GROUP sum of the forward: the channel chain, the cpg channels merged by gn_prepare, and 4 for
+    x - piv, the product by 1 / hw, piv + S / hw and the division by cpg"""
+    return gn_chain(hw, C) + C // G + 4
+
+
+def gn_k_g(hw, C, B):
+    """[N] additions behind dgamma / dbeta: the channel chain, the B images (atomics) and 4 for xhat, h, silu' and dh"""
+    return gn_chain(hw, C) + B + 4
+
+
+def gn_stats64(x, G, eps=1e-5):
+    """[N] two-pass fp64 statistics of x [B, HW, C] per (image, group) and the bounds of row N, stated about the kernel's
+    pivot piv[b, c] = x[b, 0, c] (row B's form) -> (mean [B, G], var, rstd, bound on |mean - mean64|, bound on
+    |rstd / rstd64 - 1|).  With dm_c = mean_c - piv_c and k_s = gn_k_s:
+        |mean - mean64|      <= k_s u mean|x - piv| + (cpg + 1) u mean_c|mean_c|
+        |rstd / rstd64 - 1|  <= k_s u (1 + mean_c(dm_c^2) / (var + eps)) + 2 u
+    (the sums S = sum(x - piv) and Q = sum (x - piv)^2 carry k_s u of sum|x - piv| and of hw (var_c + dm_c^2); var + eps is
+    what rstd is taken of, so the ratio is finite at var = 0; 2 u: the division and rsqrtf; (cpg + 1) u: each mean_c = piv + S / hw
+    is rounded at its own magnitude, the cpg - 1 additions of gn_prepare's chain at up to cpg mean|mean_c|, then the division
+    -- a single u |mean| is exceeded 3 x by the fp32 emulation at cpg = 48, |mean| = 100 std).  Plain torch on x's device."""
+    x = x.to(F64)
+    B, HW, C = x.shape
+    xg = x.view(B, HW, G, C // G)
+    mean = xg.mean((1, 3))
+    var = ((xg - mean.view(B, 1, G, 1)) ** 2).mean((1, 3))
+    rstd = 1.0 / torch.sqrt(var + eps)
+    piv = x[:, :1, :]
+    absdev = (x - piv).abs().mean(1).view(B, G, C // G).mean(2)
+    mc = x.mean(1, keepdim=True)
+    dm2 = ((mc - piv) ** 2).view(B, G, C // G).mean(2)
+    k = gn_k_s(HW, C, G) * U32
+    bm = k * absdev + (C // G + 1) * U32 * mc.abs().view(B, G, C // G).mean(2)
+    return mean, var, rstd, bm, k * (1.0 + dm2 / (var + eps)) + 2 * U32
+
+
+def check_gn_stats(x, G, mr, what, eps=1e-5):
+    """[N] mr [B, G, 2] = the (mean, rstd) a forward wrote, against gn_stats64's bounds -> (mean ratio, rstd ratio)"""
+    mean64, _, rstd64, bm, br = gn_stats64(x, G, eps)
+    mr = mr.to(F64).to(mean64.device)
+    rm = ((mr[..., 0] - mean64).abs() / (bm + 1e-300)).max().item()
+    rr = ((mr[..., 1] / rstd64 - 1).abs() / br).max().item()
+    assert rm <= 1.0, f"{what}: mean off by {rm:.3g} x its bound"
+    assert rr <= 1.0, f"{what}: rstd off by {rr:.3g} x its bound"
+    return rm, rr
+
+
+def _per_channel(t, C):
+    """[B, G] -> [B, 1, C]"""
+    B, G = t.shape
+    return t.view(B, G, 1).expand(B, G, C // G).reshape(B, 1, C)
+
+
 def gn_silu64(x, gamma, beta, G, eps=1e-5):
     """[N] y = silu(gamma (x - mean) rstd + beta) per (image, group), two-pass fp64 statistics; x [B, HW, C] ->
     (y64, slack, z64, xhat64, rstd64[B, G])"""
@@ -359,7 +434,41 @@ def gn_silu64(x, gamma, beta, G, eps=1e-5):
     # z = x sc + sh in fp32 (norm.hip:184): 2^-22 (|x sc| + |sh|) before the activation, then [G]'s 2^-20 |z|
     sh = beta.to(F64) - (mu.view(B, G, 1) * gamma.to(F64).view(1, G, C // G) * rstd.view(B, G, 1)).reshape(B, 1, C)
     slack = LIP["silu"] * 2.0 ** -22 * ((x * sc).abs() + sh.abs() + z.abs()) + 2.0 ** -20 * z.abs()
+    # the statistics' own error, stated about the pivot (gn_stats64): rstd scales z - beta, the mean shifts z by sc
+    _, _, _, bm, br = gn_stats64(x, G, eps)
+    slack = slack + LIP["silu"] * ((z - beta.to(F64)).abs() * _per_channel(br, C) + sc.abs() * _per_channel(bm, C))
     return act64(z, "silu"), slack, z, xh, rstd.view(B, G)
+
+
+def gn_bwd64(x, gamma, beta, gy, dres, G, eps=1e-5):
+    """[N] backward of silu(groupnorm(x)) in fp64 [+ dres] -> (dx64, dx slack, dgamma64, dbeta64, terms of dgamma / dbeta).
+    g' = gy silu'(z);  dx = rstd (gamma g' - mean(gamma g') - xhat mean(gamma g' xhat)) per (image, group).
+    dx slack: 2^-19 terms (1 + |mu| rstd) + 2^-20 |dx64| [+ 2^-24 |dres|]  (terms = the formula on absolute values; fp32 z
+    carries 2^-22 (|x sc| + |sh|) into silu', hence the conditioning factor: the row-norm form), plus the rstd bound of
+    gn_stats64 times terms (3 + |z - beta|): rstd is a factor of dx, enters xhat twice in xhat mean(g' xhat) and moves silu'
+    by |silu''| |z - beta| <= |z - beta| / 2 of its relative error.
+    dgamma = sum g' xhat, dbeta = sum g' (over images and pixels); their terms: sum |g'| (|mu| rstd + |xhat| + 1), xhat being
+    good to 2^-22 of |x| rstd."""
+    x, gamma, beta, gy = x.to(F64), gamma.to(F64), beta.to(F64), gy.to(F64)
+    B, HW, C = x.shape
+    cpg = C // G
+    _, _, z, xh, rstd = gn_silu64(x, gamma, beta, G, eps)
+    gp = gy * act_grad64(z, "silu")
+    gpg = (gp * gamma).view(B, HW, G, cpg)
+    xhg = xh.view(B, HW, G, cpg)
+    r = rstd.view(B, 1, G, 1)
+    m1 = gpg.mean((1, 3), keepdim=True)
+    m2 = (gpg * xhg).mean((1, 3), keepdim=True)
+    dx64 = (r * (gpg - m1 - xhg * m2)).view(B, HW, C)
+    mu_r = (x.view(B, HW, G, cpg).mean((1, 3), keepdim=True) * r).abs().expand(B, HW, G, cpg).reshape(B, HW, C)
+    terms = (r * (gpg.abs() + gpg.abs().mean((1, 3), keepdim=True) + xhg.abs() * (gpg * xhg).abs().mean((1, 3), keepdim=True))).view(B, HW, C)
+    br = _per_channel(gn_stats64(x, G, eps)[4], C)
+    dsl = 2.0 ** -19 * terms * (1 + mu_r) + 2.0 ** -20 * dx64.abs() + br * terms * (3 + (z - beta).abs())
+    if dres is not None:
+        dx64 = dx64 + dres.to(F64)
+        dsl = dsl + 2.0 ** -24 * dres.to(F64).abs()
+    pterms = (gp.abs() * (mu_r + xh.abs() + 1)).sum((0, 1))
+    return dx64, dsl, (gp * xh).sum((0, 1)), gp.sum((0, 1)), pterms
 
 
 EPS_RMS, EPS_LN = 1e-6, 1e-5
@@ -734,6 +843,239 @@ def gn_kernel_emul(x, gamma, beta, G, eps=1e-5, one_pass=False):
     sh = f32(beta.view(1, G, C // G) - mu[:, :, None] * sc.view(B, G, C // G)).reshape(B, 1, C)
     z = f32(x * sc + sh)
     return r16(act64(z, "silu"))
+
+
+def gn_pivot_inputs(B, HW, C, G, k, seed=0):
+    """gn_inputs with pixel 0 of every channel -- the kernels' pivot -- set k group-sigma above the group mean"""
+    x, gamma, beta = gn_inputs(B, HW, C, G, seed)
+    xg = x.view(B, HW, G, C // G)
+    piv = xg.mean((1, 3)) + k * xg.std((1, 3), unbiased=False)
+    x = x.clone()
+    x[:, 0, :] = r16(piv.view(B, G, 1).expand(B, G, C // G).reshape(B, C))
+    return x, gamma, beta
+
+
+def _fma32(a, b, c):
+    """fmaf on float32 arrays: the product of two fp32 is exact in fp64 (48 bits); one fp64 sum, rounded to fp32"""
+    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(np.float32)
+
+
+def _silu32(z):
+    with np.errstate(over="ignore"):
+        return z * (np.float32(1) / (np.float32(1) + np.exp(-z)))
+
+
+def _silu_grad32(z):
+    with np.errstate(over="ignore"):
+        s = np.float32(1) / (np.float32(1) + np.exp(-z))
+    return s * _fma32(z, np.float32(1) - s, np.float32(1))
+
+
+def _gn_slab_sums(a, b1, b2, tail=True):
+    """the reduction of gn_stats_kernel / gn_silu_bwd_reduce_kernel + gn_finalize_kernel on [B, hw, C] float32 terms:
+    s += a and q = fmaf(b1, b2, q) per pixel lane (pixels prow, prow + rows, ... of a 512-pixel slab), the lanes added in
+    order, the slabs added in order -> (s, q) [B, C].  Pixels a lane does not have contribute an exact + 0.  tail = False
+    leaves the ragged last slab out (a mutation)."""
+    B, hw, C = a.shape
+    rows = gn_rows(C)
+    steps = -(-GN_SLAB // rows)
+    nslab = -(-hw // GN_SLAB) if tail else hw // GN_SLAB
+    if nslab == 0:
+        return np.zeros((B, C), np.float32), np.zeros((B, C), np.float32)
+
+    def slabs(t):
+        buf = np.zeros((B, nslab, steps * rows, C), np.float32)
+        for s in range(nslab):
+            n = min(GN_SLAB, hw - s * GN_SLAB)
+            buf[:, s, :n] = t[:, s * GN_SLAB:s * GN_SLAB + n]
+        return buf.reshape(B, nslab, steps, rows, C)
+    a, b1, b2 = slabs(a), slabs(b1), slabs(b2)
+    s = np.zeros((B, nslab, rows, C), np.float32)
+    q = np.zeros((B, nslab, rows, C), np.float32)
+    for t in range(steps):
+        s = s + a[:, :, t]
+        q = _fma32(b1[:, :, t], b2[:, :, t], q)
+    fold = lambda v: np.cumsum(np.cumsum(v, axis=2, dtype=np.float32)[:, :, -1], axis=1, dtype=np.float32)[:, -1]
+    return fold(s), fold(q)
+
+
+GN_MUTATIONS = ("no_spread", "n_minus_1", "group_of_chunk", "image0_stats", "no_tail", "dres_after", "sums_no_gamma",
+                "inv_hw_for_n", "silu_grad_bf16_h", "dgamma_first_image", "sign_s2")
+
+
+def gn_kernel_emul_ordered(x, gamma, beta, G, gy=None, dres=None, eps=1e-5, mutate=None):
+    """fp32 in the order of operations of norm.hip's GroupNorm kernels -> dict(mr [B, G, 2], y, and with gy: dx, dgamma,
+    dbeta), float64 tensors of the values the kernels would store.
+    Forward: S = sum(x - piv), Q = sum (x - piv)^2 about piv = x[b, 0, c] (_gn_slab_sums); gn_prepare: mean_c = piv + S / hw,
+    M2_c = max(Q - S^2 / hw, 0), mean = sum_c mean_c / cpg, var = (sum_c M2_c + hw sum_c (mean_c - mean)^2) / (cpg hw),
+    rstd = 1 / sqrt(var + eps); sc = rstd gamma, sh = beta - mean sc, y = bf16(silu(fma(x, sc, sh))).
+    Backward: xhat = (x - mean) rstd, h = fma(xhat, gamma, beta), dh = gy silu'(h), red = (sum dh, sum dh xhat) in the same
+    order; S1 = sum_c gamma red_0 / n, S2 likewise, n = cpg hw; A = rstd gamma, B = beta - mean A, Cc = rstd^2 S2,
+    D = mean Cc - rstd S1; dx = bf16(fma(dh, A, fma(-x, Cc, D)) + dres); dgamma = sum_b red_1, dbeta = sum_b red_0.
+    Every fmaf of the source is one rounding; an a * b + c written without it is two (the compiler may contract it, which
+    only removes a rounding).  rsqrtf and __expf / rcp are numpy's correctly rounded ones.
+    mutate: one of GN_MUTATIONS (test_groupnorm_mutations_are_rejected)."""
+    f = np.float32
+    B, HW, C = x.shape
+    cpg = C // G
+    xf, ga, be = x.numpy().astype(f), gamma.numpy().astype(f), beta.numpy().astype(f)
+    piv = xf[:, :1, :]
+    d = xf - piv
+    S, Q = _gn_slab_sums(d, d, d, tail=mutate != "no_tail")
+    inv_hw = f(1) / f(HW)
+    mc = piv[:, 0] + S * inv_hw
+    m2c = np.maximum(Q - S * S * inv_hw, f(0))
+    chain = lambda v: np.cumsum(v.reshape(B, G, cpg), axis=2, dtype=f)[:, :, -1]
+    mean = chain(mc) / f(cpg)
+    dc = (mc.reshape(B, G, cpg) - mean[:, :, None]).astype(f)
+    spread = np.zeros((B, G), f)
+    for j in range(cpg):
+        spread = _fma32(dc[:, :, j], dc[:, :, j], spread)
+    n = f(cpg) * f(HW)
+    if mutate == "no_spread":
+        var = chain(m2c) / n
+    else:
+        var = (chain(m2c) + f(HW) * spread) / (n - f(1) if mutate == "n_minus_1" else n)
+    rstd = f(1) / np.sqrt(var + f(eps))
+    if mutate == "image0_stats":
+        mean, rstd = np.repeat(mean[:1], B, 0), np.repeat(rstd[:1], B, 0)
+    gidx = np.arange(C) // cpg
+    if mutate == "group_of_chunk":
+        gidx = (np.arange(C) // 8 * 8) // cpg
+    mu_c, rs_c = mean[:, gidx][:, None, :], rstd[:, gidx][:, None, :]
+    sc = rs_c * ga
+    sh = be - mu_c * sc
+    y = torch.from_numpy(_silu32(_fma32(xf, sc, sh)).astype(np.float64))
+    out = {"mr": torch.from_numpy(np.stack([mean, rstd], -1).astype(np.float64)), "y": r16(y)}
+    if gy is None:
+        return out
+    gf = gy.numpy().astype(f)
+    rbf = lambda h: torch.from_numpy(h).to(BF).float().numpy() if mutate == "silu_grad_bf16_h" else h
+    xh = (xf - mu_c) * rs_c
+    dh = gf * _silu_grad32(rbf(_fma32(xh, ga, be)))
+    red0, red1 = _gn_slab_sums(dh, dh, xh)
+    gsum = np.ones_like(ga) if mutate == "sums_no_gamma" else ga
+    a1, a2 = np.zeros((B, G), f), np.zeros((B, G), f)
+    for j in range(cpg):
+        a1 = _fma32(gsum[j::cpg][None], red0[:, j::cpg], a1)
+        a2 = _fma32(gsum[j::cpg][None], red1[:, j::cpg], a2)
+    inv_n = f(1) / (f(HW) if mutate == "inv_hw_for_n" else n)
+    m1c, m2g = (a1 * inv_n)[:, gidx][:, None, :], (a2 * inv_n)[:, gidx][:, None, :]
+    cA = rs_c * ga
+    cB = be - mu_c * cA
+    cC = rs_c * rs_c * m2g
+    if mutate == "sign_s2":
+        cC = -cC
+    cD = mu_c * cC - rs_c * m1c
+    dh = gf * _silu_grad32(rbf(_fma32(xf, cA, cB)))
+    dxf = _fma32(dh, cA, _fma32(-xf, cC, cD))
+    if dres is None:
+        dx = r16(torch.from_numpy(dxf))
+    elif mutate == "dres_after":
+        dx = r16(r16(torch.from_numpy(dxf)) + dres.to(F64))
+    else:
+        dx = r16(torch.from_numpy(dxf + dres.numpy().astype(f)))
+    bsum = lambda v: torch.from_numpy((v[0] if mutate == "dgamma_first_image" else np.cumsum(v, axis=0, dtype=f)[-1]).astype(np.float64))
+    out.update(dx=dx, dgamma=bsum(red1), dbeta=bsum(red0))
+    return out
+
+
+GN_HOST_SHAPES = [(2, 1030, 192, 32), (2, 513, 64, 32), (1, 3, 1536, 32), (2, 700, 32, 32)]
+
+
+@functools.lru_cache(maxsize=None)
+def gn_case(shape, k):
+    """inputs at pivot offset k, gy, the fp64 references without and with dres: computed once, shared, never modified"""
+    B, HW, C, G = shape
+    x, gamma, beta = gn_pivot_inputs(B, HW, C, G, k, seed=HW + C) if k else gn_inputs(B, HW, C, G, seed=HW + C)
+    gy = r16(torch.randn(B, HW, C, generator=torch.Generator().manual_seed(2), dtype=F64))
+    y64, ysl, *_ = gn_silu64(x, gamma, beta, G)
+    ref0 = gn_bwd64(x, gamma, beta, gy, None, G)
+    dres = rownorm_dres(ref0[0].view(B * HW, C), seed=HW).view(B, HW, C)
+    ref1 = gn_bwd64(x, gamma, beta, gy, dres, G)
+    return x, gamma, beta, gy, dres, (y64, ysl), ref0, ref1
+
+
+def gn_check_all(case, shape, out0, out1, what, bias=True):
+    """every bound of row N on an emulation's (or a kernel's) outputs without (out0) and with dres (out1) -> ratios.
+    bias = False: the rounding-bias check of check_one_rounding is reported, not asserted (a kernel at an outlier pivot: the
+    error of rstd is one signed factor on every z - beta of a group, up to the slack, which that check reads as a bias of up
+    to 1/16 ulp on the elements it samples)."""
+    B, HW, C, G = shape
+    x, gamma, beta, gy, dres, (y64, ysl), ref0, ref1 = case
+    c = max(64.0, gn_k_g(HW, C, B))
+    nb = 2000 if bias else 1 << 62
+    res = {"mean,rstd": check_gn_stats(x, G, out0["mr"], what + " statistics"),
+           "y": check_one_rounding(out0["y"], y64, ysl, what + " y", min_bias_n=nb),
+           "dx": check_one_rounding(out0["dx"], ref0[0], ref0[1], what + " dx", min_bias_n=nb),
+           "dx+dres": check_one_rounding(out1["dx"], ref1[0], ref1[1], what + " dx + dres", min_bias_n=nb),
+           "dgamma": (check_fp32(out0["dgamma"], ref0[2], ref0[4], c, what + " dgamma"),),
+           "dbeta": (check_fp32(out0["dbeta"], ref0[3], ref0[4], c, what + " dbeta"),)}
+    return {k: tuple(round(v, 4) for v in t) for k, t in res.items()}
+
+
+@pytest.mark.parametrize("k", [0, 8, 64])
+@pytest.mark.parametrize("shape", GN_HOST_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_groupnorm_ordered_emulation_sits_inside_every_bound(shape, k):
+    """[N] the fp32 emulation in the kernels' order: mean / rstd, y, dx without and with dres, dgamma, dbeta, at pivot
+    offsets of 0 / 8 / 64 group-sigma.  The bounds were never fitted to a kernel."""
+    B, HW, C, G = shape
+    case = gn_case(shape, k)
+    x, gamma, beta, gy, dres = case[:5]
+    out0 = gn_kernel_emul_ordered(x, gamma, beta, G, gy, None)
+    out1 = gn_kernel_emul_ordered(x, gamma, beta, G, gy, dres)
+    assert torch.equal(out0["y"], out1["y"]) and torch.equal(out0["mr"], out1["mr"])
+    print(f"[error-budget-host] GroupNorm {shape} pivot +{k} sigma: {gn_check_all(case, shape, out0, out1, 'clean emulation')}")
+
+
+def gn_spread_inputs(shape, seed=0):
+    """gn_inputs at |mean| <= 3 std whose channels sit -2 .. 2 group-std apart inside a group: the between-channel term"""
+    B, HW, C, G = shape
+    g = torch.Generator().manual_seed(seed)
+    cpg = C // G
+    std = 10.0 ** (torch.rand(B, 1, G, 1, generator=g, dtype=F64) * 4 - 2)
+    mean = std * (torch.rand(B, 1, G, 1, generator=g, dtype=F64) * 6 - 3 + torch.linspace(-2, 2, cpg, dtype=F64).view(1, 1, 1, cpg))
+    x = mean + std * torch.randn(B, HW, G, cpg, generator=g, dtype=F64)
+    _, gamma, beta = gn_inputs(1, 1, C, G, seed)
+    return r16(x.view(B, HW, C)), gamma, beta
+
+
+# mutation -> (host shape, the check that must reject it)
+GN_MUTATION_CASES = {
+    "no_spread": ((2, 513, 64, 32), "statistics"),
+    "n_minus_1": ((1, 3, 1536, 32), "statistics"),
+    "group_of_chunk": ((2, 1030, 192, 32), "y"),
+    "image0_stats": ((2, 513, 64, 32), "statistics"),
+    "no_tail": ((2, 513, 64, 32), "statistics"),
+    "dres_after": ((1, 3, 1536, 32), "dx + dres"),
+    "sums_no_gamma": ((2, 513, 64, 32), "dx"),
+    "inv_hw_for_n": ((2, 513, 64, 32), "dx"),
+    "silu_grad_bf16_h": ((2, 513, 64, 32), "dx"),
+    "dgamma_first_image": ((2, 513, 64, 32), "dgamma"),
+    "sign_s2": ((2, 513, 64, 32), "dx"),
+}
+
+
+@pytest.mark.parametrize("mutation", GN_MUTATIONS)
+def test_groupnorm_mutations_are_rejected(mutation):
+    """[N] each defect of GN_MUTATIONS in the ordered emulation is rejected by the bound named in GN_MUTATION_CASES, at the
+    smallest host shape that can show it, while the clean emulation passes on the same inputs.  no_spread runs on
+    gn_spread_inputs (in gn_inputs the channels of a group share their mean and the term is noise).  All eleven are
+    rejected: none of them is invisible in the outputs."""
+    shape, which = GN_MUTATION_CASES[mutation]
+    B, HW, C, G = shape
+    if mutation == "no_spread":
+        x, gamma, beta = gn_spread_inputs(shape, seed=3)
+        check_gn_stats(x, G, gn_kernel_emul_ordered(x, gamma, beta, G)["mr"], "clean emulation, spread inputs")
+        with pytest.raises(AssertionError, match="rstd"):
+            check_gn_stats(x, G, gn_kernel_emul_ordered(x, gamma, beta, G, mutate=mutation)["mr"], mutation)
+        return
+    case = gn_case(shape, 0)
+    x, gamma, beta, gy, dres = case[:5]
+    bad0 = gn_kernel_emul_ordered(x, gamma, beta, G, gy, None, mutate=mutation)
+    bad1 = gn_kernel_emul_ordered(x, gamma, beta, G, gy, dres, mutate=mutation)
+    with pytest.raises(AssertionError, match=re.escape(f"{mutation} {which}")):
+        gn_check_all(case, shape, bad0, bad1, mutation)
 
 
 def test_groupnorm_one_pass_variance_is_rejected():
