@@ -30,12 +30,15 @@ integrate the velocity field with Euler steps and classifier-free guidance and d
 (transvae/evaluate_dit.py, transvae/metrics_gen.py, csrc/genmetrics.hip): `evaluate_dit` samples, extracts Inception features and
 returns gFID, Inception Score (`InceptionScore`) and the k-NN precision / recall (`knn_radius`, `manifold_hits`,
 `precision_recall`) against a `reference_statistics` dict; `ParamEMA` (transvae/optim.py) is the weight average they are measured on,
-kept by `fit_dit(..., ema_decay=...)`.
+kept by `fit_dit(..., ema_decay=...)`.  `LightningDiT` / `create_lightning_dit` (transvae/lightning_dit.py, csrc/lightning.hip)
+are the same model with the LightningDiT block: RMSNorm adaLN with a learned weight, per-head qk-norm before the RoPE and a SwiGLU MLP,
+each behind a switch; the training, sampling and evaluation entry points above take it unchanged.
 """
 from .dit import DiT, create_dit, fit_dit, flow_matching_loss, sample_images, sample_latents
 from .evaluate import evaluate
 from .evaluate_dit import evaluate_dit
 from .generate import interpolate_latents, random_samples, reconstruct
+from .lightning_dit import LightningDiT, create_lightning_dit
 from .latents import LatentStats, extract_latents, latent_density_metrics, latent_points, latent_space_metrics
 from .image_io import ImagePrep, UInt8Batch, collate_uint8, save_image, to_uint8_grid
 from .losses.lpips import PerceptualLoss
@@ -55,4 +58,5 @@ __all__ = ["TransVAE", "create_transvae", "TransVAELoss", "reconstruction_metric
            "collate_uint8", "to_uint8_grid", "save_image", "random_samples", "interpolate_latents", "reconstruct", "LatentStats",
            "extract_latents", "latent_points", "latent_density_metrics", "latent_space_metrics", "probe_rows", "softmax_xent", "LinearProbe",
            "fit_linear_probe", "linear_probe_accuracy", "DiT", "create_dit", "flow_matching_loss", "sample_latents", "sample_images", "fit_dit",
-           "evaluate_dit", "InceptionScore", "knn_radius", "manifold_hits", "precision_recall", "reference_statistics", "ParamEMA"]
+           "evaluate_dit", "InceptionScore", "knn_radius", "manifold_hits", "precision_recall", "reference_statistics", "ParamEMA",
+           "LightningDiT", "create_lightning_dit"]

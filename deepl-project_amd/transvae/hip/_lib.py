@@ -140,6 +140,14 @@ SIGNATURES = {
     "tv_flow_loss_partial_count": (_LL, [_I, _I, _I, _I, _I, _I]),
     "tv_flow_loss": (_I, [_P, _P, _LL, _LL, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "tv_flow_euler": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P]),
+    "tv_adaln_rms_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _F, _P]),
+    "tv_adaln_rms_bwd_partial_count": (_LL, [_I, _I, _I]),
+    "tv_adaln_rms_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
+    "tv_qknorm_rope_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
+    "tv_qknorm_rope_bwd_partial_count": (_LL, [_I, _I, _I]),
+    "tv_qknorm_rope_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
+    "tv_swiglu_fwd": (_I, [_P, _P, _LL, _I, _P]),
+    "tv_swiglu_bwd": (_I, [_P, _P, _P, _LL, _I, _P]),
     "tv_knn_radius": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "tv_manifold_hits": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P]),
     "tv_softmax_stats": (_I, [_P, _I, _I, _I, _P, _P, _P]),

@@ -612,6 +612,44 @@ int tv_flow_loss(const void* pred, const float* lat, long long sn, long long sc,
                  void* dpred, double* out, double* partials, int B, int D, int h, int w, int patch, int ld, float grad_scale, void* stream);
 int tv_flow_euler(float* x, const void* v, int B, int D, int h, int w, int patch, int ld, float dt, float cfg_scale, int guided, void* stream);
 
+/* LightningDiT block variants: RMSNorm adaLN, per-head qk-norm with RoPE, SwiGLU (csrc/lightning.hip) -----------------------------------
+ * The conventions of the DiT block above: bf16 token matrices [B N, C], 16-byte aligned, C % 8 == 0; the fp32 [B, ld] modulation
+ * matrix read by column offsets; every sum that crosses rows goes through scratch partials in a fixed order and is WRITTEN (no
+ * accumulation, no atomics anywhere in the file: the same bits on every run).  Rounding contract: DESIGN.md section 3.1 row J;
+ * protocol: section 3.6.
+ * tv_adaln_rms_fwd: xhat = x rsqrt(mean(x^2) + eps) (one fp32 chain per lane, a butterfly; no mean), z = xhat w rounded once (w fp32
+ * [C]), y = bf16(fma(z, 1 + scale, shift)).  One wave per row, C <= 1536.
+ * tv_adaln_rms_bwd: the statistic recomputed; g = dy ((1 + scale) w); dx = bf16(rstd (g - xhat mean(g xhat)) + dres) (dres bf16 or
+ * NULL, joined in fp32); dmod[b, shift_off + c] = sum_n dy; with S[b, c] = sum_n dy xhat (per wave its 16 rows of a 64-row slab,
+ * the four waves, the slabs of a sample, all in order): dmod[b, scale_off + c] = w[c] S[b, c] and dw[c] = sum_b fma(1 + scale[b, c],
+ * S[b, c], .) (sample b in lane b % 16 in order, the sixteen lanes in order), fp32 [C], written.  The two ranges must not overlap.
+ * partials: tv_adaln_rms_bwd_partial_count(B, N, C) floats of scratch. */
+int tv_adaln_rms_fwd(const void* x, const float* w, const float* mod, int shift_off, int scale_off, int ld, void* y, int B, int N, int C, float eps,
+                     void* stream);
+long long tv_adaln_rms_bwd_partial_count(int B, int N, int C);
+int tv_adaln_rms_bwd(const void* x, const float* w, const float* mod, int shift_off, int scale_off, int ld, const void* dy, const void* dres, void* dx,
+                     float* dmod, float* dw, float* partials, int B, int N, int C, float eps, void* stream);
+/* Per-head RMSNorm of q and k, then the RoPE of tv_rope_qk, on qkv [B, N, 3, heads, 64] bf16; wq, wk fp32 [64]; rope_tab [N, 4, 32]
+ * fp32 or NULL (no rotation).
+ * tv_qknorm_rope_fwd: per (token, head), q and k alike: r = rsqrt(mean_64(q^2) + eps) (eight lanes of 16 bytes, a three-step
+ * butterfly), z = (q r) w, rotated in fp32 (two products and their sum per output, as tv_rope_qk), rounded to bf16 once; the v third
+ * is copied bit for bit.  out may be qkv itself (each 64-vector is read whole before it is written) or must not overlap it.
+ * tv_qknorm_rope_bwd: qkv holds the RAW projections, dqkv the gradient from tv_attn_bwd called WITH the table (so dq / dk are
+ * gradients of the un-rotated z).  In place on dqkv: g = dq wq, qh = q r, dq_raw = bf16(r fma(-qh, mean_64(g qh), g)); k likewise; v
+ * untouched.  dwq[j] = sum over (b, n, head) of dq_j qh_j and dwk likewise, fp32 [64], written: per lane group its vectors in pass
+ * order, the 32 groups of a block in order, block k in lane k % 64 in order, the 64 lanes in order.  A zero head vector gives
+ * exactly 0 forward and a finite gradient.  partials: tv_qknorm_rope_bwd_partial_count(B, N, heads) floats of scratch. */
+int tv_qknorm_rope_fwd(const void* qkv, const float* wq, const float* wk, const float* rope_tab, void* out, int B, int N, int heads, float eps,
+                       void* stream);
+long long tv_qknorm_rope_bwd_partial_count(int B, int N, int heads);
+int tv_qknorm_rope_bwd(const void* qkv, const float* wq, const float* wk, void* dqkv, float* dwq, float* dwk, float* partials, int B, int N, int heads,
+                       float eps, void* stream);
+/* SwiGLU on u bf16 [T, 2 Hp] = [x1 | x2], Hp % 32 == 0: h [T, Hp] = bf16((x1 s) x2), s = 1 / (1 + expf(-x1)) with the IEEE division.
+ * tv_swiglu_bwd: du [T, 2 Hp] = [bf16((dh x2) (s fma(x1, 1 - s, 1))) | bf16(dh (x1 s))].  Finite for every finite bf16 x1 (at
+ * x1 = -3e38: silu = -0, derivative -0; at +3e38: silu = x1, derivative 1); x1 = 0 gives exactly 0. */
+int tv_swiglu_fwd(const void* u, void* h, long long T, int Hp, void* stream);
+int tv_swiglu_bwd(const void* u, const void* dh, void* du, long long T, int Hp, void* stream);
+
 
 /* Generation metrics (csrc/genmetrics.hip) -------------------------------------------------------------------------------------------
  * Squared distance of the two pairwise kernels: D(a, b) = sum_c (a_c - b_c)^2 as ONE fp32 chain over c = 0 .. d - 1 in order, diff =
