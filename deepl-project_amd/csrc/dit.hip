@@ -1,10 +1,13 @@
-// Latent DiT: the adaLN-Zero conditioning arithmetic and the flow-matching edge (transvae/dit.py drives them; the token GEMMs and
-// attention are tv_igemm_nt / tv_wgrad_tn / tv_attn_*).  DESIGN.md section 3.1 row E holds the rounding contract, section 3.4 the
-// protocol.  Rows are tokens: row r of a [B N, C] matrix belongs to sample r / N, whose modulation is row r / N of an fp32 [B, ld]
-// matrix; shift / scale / gate are column ranges of it, given as offsets.
+// Latent DiT: the adaLN conditioning arithmetic of its two block variants and the flow-matching edge (transvae/dit.py and
+// transvae/lightning_dit.py drive them; the token GEMMs and attention are tv_igemm_nt / tv_wgrad_tn / tv_attn_*).  DESIGN.md section 3.1
+// rows E and J hold the rounding contracts, sections 3.4 and 3.6 the protocols.  Rows are tokens: row r of a [B N, C] matrix belongs to
+// sample r / N, whose modulation is row r / N of an fp32 [B, ld] matrix; shift / scale / gate are column ranges of it, given as offsets.
 //
 //   tv_adaln_fwd           y = bf16(fma(xhat, 1 + scale, shift)), xhat = (x - mean) rstd, two-pass statistics, one wave per row
 //   tv_adaln_bwd           dx = bf16(rstd (g - mean g - xhat mean(g xhat)) + dres), g = dy (1 + scale); dshift = sum_n dy, dscale = sum_n dy xhat
+//   tv_adaln_rms_fwd       y = bf16(fma(z, 1 + scale, shift)), z = xhat w (one rounding), xhat = x rsqrt(mean(x^2) + eps); the same kernel, RMS = true
+//   tv_adaln_rms_bwd       dx = bf16(rstd (g - xhat mean(g xhat)) + dres), g = dy ((1 + scale) w); dshift = sum_n dy; with
+//                          S = sum_n dy xhat: dscale = w S, dw = sum_b (1 + scale_b) S_b
 //   tv_gate_residual_fwd   out = bf16(fma(gate, y, x))
 //   tv_gate_residual_bwd   dy = bf16(gate dout); dgate = sum_n dout y
 //   tv_flow_rows           patch rows of x_t = fma(t, x, (1 - t) e), x = (lat - mean) rstd   (no noise: the rows of x)
@@ -14,12 +17,14 @@
 // The per-sample sums never cross a sample inside a block: the grids of the reducing kernels are cut per sample (blockIdx.y = sample,
 // blockIdx.x = a slab of its rows), so a row count that is no multiple of the slab leaves a short last slab instead of a block that
 // straddles two samples.  Every sum is taken in a fixed order (lane: its rows in order; block: its waves or row lanes in order;
-// finalise: the slabs in order): no atomics, the same bits on every run.
+// finalise: the slabs in order; for the dw of tv_adaln_rms_bwd then sixteen sample lanes, sample b in lane b % 16 in order, and the
+// lanes in order): no atomics, the same bits on every run.
 //
-// Algorithmic bytes per call (what tools/dit_bench.py divides by kernel time), T = B N rows:
-//   tv_adaln_fwd  4 T C        tv_adaln_bwd  6 T C (8 T C with dres)      tv_gate_residual_fwd  6 T C      tv_gate_residual_bwd  6 T C
+// Algorithmic bytes per call (what tools/dit_bench.py and tools/lightning_dit_bench.py divide by kernel time), T = B N rows:
+//   tv_adaln_fwd, tv_adaln_rms_fwd  4 T C        tv_adaln_bwd, tv_adaln_rms_bwd  6 T C (8 T C with dres)
+//   tv_gate_residual_fwd  6 T C      tv_gate_residual_bwd  6 T C
 //   tv_flow_rows  4 B D h w (8 with noise) + 2 T ld     tv_flow_loss  8 B D h w + 4 T ld     tv_flow_euler  8 B D h w + 2 T ld (4 guided)
-#include "common.h"
+#include "row_wave.h"
 
 #include <math.h>
 
@@ -29,137 +34,102 @@ namespace {
 
 constexpr int AD_RPB = 64;          // rows of one sample per block (4 waves x 16 rows)
 constexpr int AD_MAX_C = 1536;      // 3 chunks per lane; the backward's LDS is 32 C bytes
+constexpr int AD_DW_LANES = 16;     // sample lanes of the dw sum
 constexpr int GR_RPB = 64;
 constexpr int GR_MAX_C = 2048;      // one 16-byte chunk per thread column
 constexpr int FL_MAX_BLOCKS = 1024;
 
-template <int KCH>
-struct AdRow {
-    float v[KCH][8];   // x - mean (0 in the lanes past the row)
-    float rstd;
-};
-
-// two-pass statistics of one row held by a wave (the scheme of tv_rownorm_fwd mode 2)
-template <int KCH>
-__device__ __forceinline__ void ad_load_row(const bf16* __restrict__ xr, int lane, int nch, float inv_c, float eps, AdRow<KCH>& r) {
-    float su = 0.f;
+// xhat of one row held by a wave (row_wave.h), in place; returns rstd
+//   RMS = false  two passes: the mean, then the squared deviations from it (the scheme of tv_rownorm_fwd mode 2); xhat = (x - mean) rstd
+//   RMS = true   one fma chain per lane over its elements, a butterfly, no mean; xhat = x rstd
+template <int KCH, bool RMS>
+__device__ __forceinline__ float ad_load_xhat(const bf16* __restrict__ xr, int lane, int nch, float inv_c, float eps, float (&v)[KCH][8]) {
+    rw_load<KCH>(xr, lane, nch, v);
+    float sv;
+    if constexpr (RMS) sv = rw_sumsq<KCH>(v);
+    else sv = rw_centre<KCH>(v, lane, nch, rw_sum<KCH>(v) * inv_c);
+    const float rstd = rsqrtf(sv * inv_c + eps);
 #pragma unroll
-    for (int k = 0; k < KCH; ++k) {
-        const int ch = lane + 64 * k;
-        bf16x8 t = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (ch < nch) t = *(const bf16x8*)(xr + ch * 8);
+    for (int k = 0; k < KCH; ++k)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            r.v[k][e] = (float)t[e];
-            su += r.v[k][e];
-        }
-    }
-    const float mu = tv_wave_sum(su) * inv_c;
-    float sv = 0.f;
-#pragma unroll
-    for (int k = 0; k < KCH; ++k) {
-        const int ch = lane + 64 * k;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            r.v[k][e] = (ch < nch) ? r.v[k][e] - mu : 0.f;
-            sv = fmaf(r.v[k][e], r.v[k][e], sv);
-        }
-    }
-    r.rstd = rsqrtf(tv_wave_sum(sv) * inv_c + eps);
+        for (int e = 0; e < 8; ++e) v[k][e] *= rstd;
+    return rstd;
 }
 
-template <int KCH>
-__global__ __launch_bounds__(256) void adaln_fwd_kernel(const bf16* __restrict__ x, const float* __restrict__ mod, int shift_off, int scale_off,
-                                                        int ld, bf16* __restrict__ y, int N, int C, float eps) {
+// RMS: xhat = x rstd is scaled by the weight w before the modulation (tv_adaln_rms_fwd); otherwise w is not read
+template <int KCH, bool RMS>
+__global__ __launch_bounds__(256) void adaln_fwd_kernel(const bf16* __restrict__ x, const float* __restrict__ w, const float* __restrict__ mod,
+                                                        int shift_off, int scale_off, int ld, bf16* __restrict__ y, int N, int C, float eps) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nch = C >> 3, b = blockIdx.y;
     const float inv_c = 1.0f / (float)C;
     const float* __restrict__ mb = mod + (size_t)b * ld;
-    float sc1[KCH][8], sh[KCH][8];
-#pragma unroll
-    for (int k = 0; k < KCH; ++k) {
-        const int ch = lane + 64 * k;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            sc1[k][e] = (ch < nch) ? 1.0f + mb[scale_off + ch * 8 + e] : 0.f;
-            sh[k][e] = (ch < nch) ? mb[shift_off + ch * 8 + e] : 0.f;
-        }
-    }
+    float sc1[KCH][8], sh[KCH][8], wv[KCH][8];
+    rw_load_cols<KCH, true>(mb + scale_off, lane, nch, 0.f, sc1);
+    rw_load_cols<KCH>(mb + shift_off, lane, nch, 0.f, sh);
+    if constexpr (RMS) rw_load_cols<KCH>(w, lane, nch, 0.f, wv);
     const int r0 = blockIdx.x * AD_RPB, r1 = min(N, r0 + AD_RPB);
     for (int n = r0 + wave; n < r1; n += 4) {                // (wave-uniform)
         const size_t row = (size_t)b * N + n;
-        AdRow<KCH> r;
-        ad_load_row<KCH>(x + row * C, lane, nch, inv_c, eps, r);
-#pragma unroll
-        for (int k = 0; k < KCH; ++k) {
-            const int ch = lane + 64 * k;
-            if (ch < nch) {
-                bf16x8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = (bf16)fmaf(r.v[k][e] * r.rstd, sc1[k][e], sh[k][e]);
-                *(bf16x8*)(y + row * C + ch * 8) = o;
-            }
-        }
+        float xh[KCH][8];
+        ad_load_xhat<KCH, RMS>(x + row * C, lane, nch, inv_c, eps, xh);
+        rw_store<KCH>(y, nullptr, row * C, lane, nch, [&](int k, int e, float) {
+            float z = xh[k][e];
+            if constexpr (RMS) z *= wv[k][e];
+            return fmaf(z, sc1[k][e], sh[k][e]);
+        });
     }
 }
 
-template <int KCH>
-__global__ __launch_bounds__(256) void adaln_bwd_kernel(const bf16* __restrict__ x, const float* __restrict__ mod, int scale_off, int ld,
-                                                        const bf16* __restrict__ dy, const bf16* __restrict__ dres, bf16* __restrict__ dx,
-                                                        float* __restrict__ part, int N, int C, float eps) {
+// RMS: g = dy ((1 + scale) w) and no `- mean g` term (tv_adaln_rms_bwd); part[b][slab] = {sum_n dy, sum_n dy xhat} either way
+template <int KCH, bool RMS>
+__global__ __launch_bounds__(256) void adaln_bwd_kernel(const bf16* __restrict__ x, const float* __restrict__ w, const float* __restrict__ mod,
+                                                        int scale_off, int ld, const bf16* __restrict__ dy, const bf16* __restrict__ dres,
+                                                        bf16* __restrict__ dx, float* __restrict__ part, int N, int C, float eps) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* s_acc = (float*)smem;      // [4 waves][2][C]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nch = C >> 3, b = blockIdx.y;
     const float inv_c = 1.0f / (float)C;
-    const float* __restrict__ mb = mod + (size_t)b * ld;
-    float sc1[KCH][8], ds[KCH][8], dq[KCH][8];
+    float gs[KCH][8], ds[KCH][8], dq[KCH][8];      // gs: the factor of g = dy gs
+    rw_load_cols<KCH, true>(mod + (size_t)b * ld + scale_off, lane, nch, 0.f, gs);
+    if constexpr (RMS) {
+        float wv[KCH][8];
+        rw_load_cols<KCH>(w, lane, nch, 0.f, wv);
 #pragma unroll
-    for (int k = 0; k < KCH; ++k) {
-        const int ch = lane + 64 * k;
+        for (int k = 0; k < KCH; ++k)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            sc1[k][e] = (ch < nch) ? 1.0f + mb[scale_off + ch * 8 + e] : 0.f;
-            ds[k][e] = dq[k][e] = 0.f;
-        }
+            for (int e = 0; e < 8; ++e) gs[k][e] *= wv[k][e];   // (1 + scale) w, rounded once per channel
     }
+#pragma unroll
+    for (int k = 0; k < KCH; ++k)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) ds[k][e] = dq[k][e] = 0.f;
     const int r0 = blockIdx.x * AD_RPB, r1 = min(N, r0 + AD_RPB);
     for (int n = r0 + wave; n < r1; n += 4) {                // (wave-uniform)
         const size_t row = (size_t)b * N + n;
-        AdRow<KCH> r;
-        ad_load_row<KCH>(x + row * C, lane, nch, inv_c, eps, r);
-        float g[KCH][8];
+        float xh[KCH][8], g[KCH][8];
+        const float rstd = ad_load_xhat<KCH, RMS>(x + row * C, lane, nch, inv_c, eps, xh);
+        rw_load<KCH>(dy + row * C, lane, nch, g);
         float a1 = 0.f, a2 = 0.f;
 #pragma unroll
-        for (int k = 0; k < KCH; ++k) {
-            const int ch = lane + 64 * k;
-            bf16x8 u = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (ch < nch) u = *(const bf16x8*)(dy + row * C + ch * 8);
+        for (int k = 0; k < KCH; ++k)
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const float d = (float)u[e];
-                r.v[k][e] *= r.rstd;                           // xhat
-                g[k][e] = d * sc1[k][e];
-                a1 += g[k][e];
-                a2 = fmaf(g[k][e], r.v[k][e], a2);
+                const float d = g[k][e];
+                g[k][e] = d * gs[k][e];
+                if constexpr (!RMS) a1 += g[k][e];
+                a2 = fmaf(g[k][e], xh[k][e], a2);
                 ds[k][e] += d;
-                dq[k][e] = fmaf(d, r.v[k][e], dq[k][e]);
+                dq[k][e] = fmaf(d, xh[k][e], dq[k][e]);
             }
-        }
-        a1 = tv_wave_sum(a1) * inv_c;
+        if constexpr (!RMS) a1 = tv_wave_sum(a1) * inv_c;
         a2 = tv_wave_sum(a2) * inv_c;
-#pragma unroll
-        for (int k = 0; k < KCH; ++k) {
-            const int ch = lane + 64 * k;
-            if (ch < nch) {
-                bf16x8 rv = {0, 0, 0, 0, 0, 0, 0, 0};
-                if (dres) rv = *(const bf16x8*)(dres + row * C + ch * 8);
-                bf16x8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = (bf16)(r.rstd * fmaf(-r.v[k][e], a2, g[k][e] - a1) + (float)rv[e]);
-                *(bf16x8*)(dx + row * C + ch * 8) = o;
-            }
-        }
+        rw_store<KCH>(dx, dres, row * C, lane, nch, [&](int k, int e, float res) {
+            float t = g[k][e];
+            if constexpr (!RMS) t -= a1;
+            return rstd * fmaf(-xh[k][e], a2, t) + res;
+        });
     }
 #pragma unroll
     for (int k = 0; k < KCH; ++k) {
@@ -182,9 +152,10 @@ __global__ __launch_bounds__(256) void adaln_bwd_kernel(const bf16* __restrict__
     }
 }
 
-// out[b][off(set) + c] = sum over the slabs of part[b][slab][set][c], in slab order
-__global__ __launch_bounds__(256) void mod_finalize_kernel(const float* __restrict__ part, float* __restrict__ out, int nblk, int nsets, int C, int ld,
-                                                           int off0, int off1) {
+// out[b][off(set) + c] = sum over the slabs of part[b][slab][set][c], in slab order.  With w (tv_adaln_rms_bwd) set 1 is
+// S = sum_n dy xhat: dscale[b][c] = w[c] S, and S is kept in sums[b][c] for the dw pass
+__global__ __launch_bounds__(256) void mod_finalize_kernel(const float* __restrict__ part, const float* __restrict__ w, float* __restrict__ out,
+                                                           float* __restrict__ sums, int nblk, int nsets, int C, int ld, int off0, int off1) {
     const int b = blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;
     const int n = nsets * C;
@@ -193,7 +164,33 @@ __global__ __launch_bounds__(256) void mod_finalize_kernel(const float* __restri
     float a = 0.f;
     for (int k = 0; k < nblk; ++k) a += src[(size_t)k * n];
     const int set = i / C, c = i - set * C;
+    if (w && set == 1) {
+        sums[(size_t)b * C + c] = a;
+        a = w[c] * a;
+    }
     out[(size_t)b * ld + (set == 0 ? off0 : off1) + c] = a;
+}
+
+// dw[c] = sum_b fma(1 + scale[b][c], S[b][c], .): sample b in lane b % 16 in order, then the sixteen lanes in order.  A block is 16
+// columns x 16 sample lanes, so that the B / 16 dependent steps of a lane (not B of them) bound the launch.
+__global__ __launch_bounds__(256) void rms_dw_kernel(const float* __restrict__ sums, const float* __restrict__ mod, int scale_off, int ld,
+                                                     float* __restrict__ dw, int B, int C) {
+    __shared__ float s_acc[AD_DW_LANES][16];
+    const int col = threadIdx.x & 15, bl = threadIdx.x >> 4;
+    const int c = blockIdx.x * 16 + col;
+    float a = 0.f;
+    if (c < C) {
+#pragma unroll 4
+        for (int b = bl; b < B; b += AD_DW_LANES) a = fmaf(1.0f + mod[(size_t)b * ld + scale_off + c], sums[(size_t)b * C + c], a);
+    }
+    s_acc[bl][col] = a;
+    __syncthreads();
+    if (bl == 0 && c < C) {
+        float t = 0.f;
+#pragma unroll
+        for (int i = 0; i < AD_DW_LANES; ++i) t += s_acc[i][col];
+        dw[c] = t;
+    }
 }
 
 __global__ __launch_bounds__(256) void gate_fwd_kernel(const bf16* __restrict__ x, const bf16* __restrict__ y, const float* __restrict__ mod, int gate_off,
@@ -372,6 +369,40 @@ int ad_check(const char* name, int B, int N, int C, int ld, int max_c) {
 
 bool ad_range(int off, int C, int ld) { return off >= 0 && (long long)off + C <= ld; }
 
+// tv_adaln_fwd (w unused) and tv_adaln_rms_fwd
+template <bool RMS>
+int adaln_fwd(const char* name, const void* x, const float* w, const float* mod, int shift_off, int scale_off, int ld, void* y, int B, int N, int C,
+              float eps, void* stream) {
+    if (ad_check(name, B, N, C, ld, AD_MAX_C)) return TV_ERR_ARG;
+    TV_CHECK_ARG(x && (w || !RMS) && mod && y, "%s: null pointer", name);
+    TV_CHECK_ARG(ad_range(shift_off, C, ld) && ad_range(scale_off, C, ld), "%s: column ranges %d / %d + %d outside ld=%d", name, shift_off, scale_off, C,
+                 ld);
+    TV_CHECK_ARG((((uintptr_t)x | (uintptr_t)y) & 15) == 0, "%s: x / y must be 16-byte aligned", name);
+    rw_dispatch<1, 2, 3>(tv_cdiv(C >> 3, 64), [&](auto K) {
+        hipLaunchKernelGGL((adaln_fwd_kernel<decltype(K)::value, RMS>), dim3(tv_cdiv(N, AD_RPB), B), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, w, mod,
+                           shift_off, scale_off, ld, (bf16*)y, N, C, eps);
+    });
+    TV_CHECK_LAUNCH(name);
+    return TV_OK;
+}
+
+// the row pass of tv_adaln_bwd (w, dw unused) and tv_adaln_rms_bwd: dx and the slab partials; the callers finalise
+template <bool RMS>
+int adaln_bwd(const char* name, const void* x, const float* w, const float* mod, int shift_off, int scale_off, int ld, const void* dy, const void* dres,
+              void* dx, const float* dmod, const float* dw, float* partials, int B, int N, int C, float eps, void* stream) {
+    if (ad_check(name, B, N, C, ld, AD_MAX_C)) return TV_ERR_ARG;
+    TV_CHECK_ARG(x && (w || !RMS) && mod && dy && dx && dmod && (dw || !RMS) && partials, "%s: null pointer", name);
+    TV_CHECK_ARG(ad_range(shift_off, C, ld) && ad_range(scale_off, C, ld) && (shift_off + C <= scale_off || scale_off + C <= shift_off),
+                 "%s: column ranges %d / %d + %d outside ld=%d or overlapping", name, shift_off, scale_off, C, ld);
+    TV_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dres | (uintptr_t)dx) & 15) == 0, "%s: x / dy / dres / dx must be 16-byte aligned", name);
+    rw_dispatch<1, 2, 3>(tv_cdiv(C >> 3, 64), [&](auto K) {
+        hipLaunchKernelGGL((adaln_bwd_kernel<decltype(K)::value, RMS>), dim3(tv_cdiv(N, AD_RPB), B), dim3(256), (size_t)8 * C * sizeof(float),
+                           (hipStream_t)stream, (const bf16*)x, w, mod, scale_off, ld, (const bf16*)dy, (const bf16*)dres, (bf16*)dx, partials, N, C, eps);
+    });
+    TV_CHECK_LAUNCH(name);
+    return TV_OK;
+}
+
 int flow_geo(const char* name, long long sn, long long sc, int B, int D, int h, int w, int p, int ld, FlowGeo& g) {
     if (B <= 0 || D <= 0 || h <= 0 || w <= 0 || p <= 0 || h % p != 0 || w % p != 0) {
         tv_set_error("%s: bad shape B=%d D=%d h=%d w=%d patch=%d (the patch must divide the grid)", name, B, D, h, w, p);
@@ -399,18 +430,12 @@ unsigned flow_blocks(long long total, int cap) {
 
 extern "C" int tv_adaln_fwd(const void* x, const float* mod, int shift_off, int scale_off, int ld, void* y, int B, int N, int C, float eps,
                             void* stream) {
-    if (ad_check("tv_adaln_fwd", B, N, C, ld, AD_MAX_C)) return TV_ERR_ARG;
-    TV_CHECK_ARG(x && mod && y, "tv_adaln_fwd: null pointer");
-    TV_CHECK_ARG(ad_range(shift_off, C, ld) && ad_range(scale_off, C, ld), "tv_adaln_fwd: column ranges %d / %d + %d outside ld=%d", shift_off,
-                 scale_off, C, ld);
-    TV_CHECK_ARG((((uintptr_t)x | (uintptr_t)y) & 15) == 0, "tv_adaln_fwd: x / y must be 16-byte aligned");
-    const dim3 grid(tv_cdiv(N, AD_RPB), B);
-    const int kch = tv_cdiv(C >> 3, 64);
-#define TV_AD_FWD(K) hipLaunchKernelGGL(adaln_fwd_kernel<K>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, mod, shift_off, scale_off, ld, (bf16*)y, N, C, eps)
-    if (kch <= 1) TV_AD_FWD(1); else if (kch == 2) TV_AD_FWD(2); else TV_AD_FWD(3);
-#undef TV_AD_FWD
-    TV_CHECK_LAUNCH("tv_adaln_fwd");
-    return TV_OK;
+    return adaln_fwd<false>("tv_adaln_fwd", x, nullptr, mod, shift_off, scale_off, ld, y, B, N, C, eps, stream);
+}
+
+extern "C" int tv_adaln_rms_fwd(const void* x, const float* w, const float* mod, int shift_off, int scale_off, int ld, void* y, int B, int N, int C,
+                                float eps, void* stream) {
+    return adaln_fwd<true>("tv_adaln_rms_fwd", x, w, mod, shift_off, scale_off, ld, y, B, N, C, eps, stream);
 }
 
 extern "C" long long tv_adaln_bwd_partial_count(int B, int N, int C) {
@@ -418,24 +443,31 @@ extern "C" long long tv_adaln_bwd_partial_count(int B, int N, int C) {
     return (long long)B * tv_cdiv(N, AD_RPB) * 2 * C;          // floats
 }
 
+extern "C" long long tv_adaln_rms_bwd_partial_count(int B, int N, int C) {
+    if (B <= 0 || N <= 0 || C <= 0) return -1;
+    return (long long)B * tv_cdiv(N, AD_RPB) * 2 * C + (long long)B * C;          // floats: the slab partials, then S
+}
+
 extern "C" int tv_adaln_bwd(const void* x, const float* mod, int shift_off, int scale_off, int ld, const void* dy, const void* dres, void* dx,
                             float* dmod, float* partials, int B, int N, int C, float eps, void* stream) {
-    if (ad_check("tv_adaln_bwd", B, N, C, ld, AD_MAX_C)) return TV_ERR_ARG;
-    TV_CHECK_ARG(x && mod && dy && dx && dmod && partials, "tv_adaln_bwd: null pointer");
-    TV_CHECK_ARG(ad_range(shift_off, C, ld) && ad_range(scale_off, C, ld) && (shift_off + C <= scale_off || scale_off + C <= shift_off),
-                 "tv_adaln_bwd: column ranges %d / %d + %d outside ld=%d or overlapping", shift_off, scale_off, C, ld);
-    TV_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dres | (uintptr_t)dx) & 15) == 0, "tv_adaln_bwd: x / dy / dres / dx must be 16-byte aligned");
-    const int nblk = tv_cdiv(N, AD_RPB);
-    const dim3 grid(nblk, B);
-    const int kch = tv_cdiv(C >> 3, 64);
-    const size_t lds = (size_t)8 * C * sizeof(float);
-#define TV_AD_BWD(K) hipLaunchKernelGGL(adaln_bwd_kernel<K>, grid, dim3(256), lds, (hipStream_t)stream, (const bf16*)x, mod, scale_off, ld, (const bf16*)dy, (const bf16*)dres, (bf16*)dx, partials, N, C, eps)
-    if (kch <= 1) TV_AD_BWD(1); else if (kch == 2) TV_AD_BWD(2); else TV_AD_BWD(3);
-#undef TV_AD_BWD
-    TV_CHECK_LAUNCH("tv_adaln_bwd");
-    hipLaunchKernelGGL(mod_finalize_kernel, dim3(tv_cdiv(2 * C, 256), B), dim3(256), 0, (hipStream_t)stream, (const float*)partials, dmod, nblk, 2, C, ld,
-                       shift_off, scale_off);
+    if (int rc = adaln_bwd<false>("tv_adaln_bwd", x, nullptr, mod, shift_off, scale_off, ld, dy, dres, dx, dmod, nullptr, partials, B, N, C, eps, stream))
+        return rc;
+    hipLaunchKernelGGL(mod_finalize_kernel, dim3(tv_cdiv(2 * C, 256), B), dim3(256), 0, (hipStream_t)stream, (const float*)partials, nullptr, dmod, nullptr,
+                       tv_cdiv(N, AD_RPB), 2, C, ld, shift_off, scale_off);
     TV_CHECK_LAUNCH("tv_adaln_bwd (finalise)");
+    return TV_OK;
+}
+
+extern "C" int tv_adaln_rms_bwd(const void* x, const float* w, const float* mod, int shift_off, int scale_off, int ld, const void* dy, const void* dres,
+                                void* dx, float* dmod, float* dw, float* partials, int B, int N, int C, float eps, void* stream) {
+    if (int rc = adaln_bwd<true>("tv_adaln_rms_bwd", x, w, mod, shift_off, scale_off, ld, dy, dres, dx, dmod, dw, partials, B, N, C, eps, stream)) return rc;
+    const int nblk = tv_cdiv(N, AD_RPB);
+    float* sums = partials + (size_t)B * nblk * 2 * C;
+    hipLaunchKernelGGL(mod_finalize_kernel, dim3(tv_cdiv(2 * C, 256), B), dim3(256), 0, (hipStream_t)stream, (const float*)partials, w, dmod, sums, nblk, 2, C,
+                       ld, shift_off, scale_off);
+    TV_CHECK_LAUNCH("tv_adaln_rms_bwd (finalise)");
+    hipLaunchKernelGGL(rms_dw_kernel, dim3(tv_cdiv(C, 16)), dim3(256), 0, (hipStream_t)stream, (const float*)sums, mod, scale_off, ld, dw, B, C);
+    TV_CHECK_LAUNCH("tv_adaln_rms_bwd (dw)");
     return TV_OK;
 }
 
@@ -467,8 +499,8 @@ extern "C" int tv_gate_residual_bwd(const void* dout, const void* y, const float
     hipLaunchKernelGGL(gate_bwd_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)stream, (const bf16*)dout, (const bf16*)y, mod, gate_off, ld, (bf16*)dy,
                        partials, N, C);
     TV_CHECK_LAUNCH("tv_gate_residual_bwd");
-    hipLaunchKernelGGL(mod_finalize_kernel, dim3(tv_cdiv(C, 256), B), dim3(256), 0, (hipStream_t)stream, (const float*)partials, dmod, nblk, 1, C, ld, gate_off,
-                       gate_off);
+    hipLaunchKernelGGL(mod_finalize_kernel, dim3(tv_cdiv(C, 256), B), dim3(256), 0, (hipStream_t)stream, (const float*)partials, nullptr, dmod, nullptr, nblk, 1, C, ld,
+                       gate_off, gate_off);
     TV_CHECK_LAUNCH("tv_gate_residual_bwd (finalise)");
     return TV_OK;
 }

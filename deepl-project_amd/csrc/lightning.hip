@@ -1,25 +1,20 @@
 // LightningDiT block variants of the latent DiT (transvae/lightning_dit.py drives them; the token GEMMs and attention are
 // tv_igemm_nt / tv_wgrad_tn / tv_attn_*).  DESIGN.md section 3.1 row J holds the rounding contract, section 3.6 the protocol.  The
-// conventions are those of dit.hip: token matrices are bf16 [B N, C], row r belongs to sample r / N, whose modulation is row r / N
-// of an fp32 [B, ld] matrix read by column offsets.
+// conventions are those of dit.hip, which also holds the block's RMSNorm adaLN (tv_adaln_rms_fwd / _bwd, one kernel pair with
+// tv_adaln_fwd / _bwd): token matrices are bf16 [B N, C].
 //
-//   tv_adaln_rms_fwd      y = bf16(fma(z, 1 + scale, shift)), z = xhat w (one rounding), xhat = x rsqrt(mean(x^2) + eps); one wave per row
-//   tv_adaln_rms_bwd      dx = bf16(rstd (g - xhat mean(g xhat)) + dres), g = dy ((1 + scale) w); dshift = sum_n dy; with
-//                         S = sum_n dy xhat: dscale = w S, dw = sum_b (1 + scale_b) S_b
 //   tv_qknorm_rope_fwd    per (token, head), q and k alike: r = rsqrt(mean_64(q^2) + eps), out = bf16(rope(q r w)); v copied
 //   tv_qknorm_rope_bwd    in place on dqkv: dq_raw = bf16(r (g - qh mean_64(g qh))), g = dq w, qh = q r; dw_j = sum dq_j qh_j
 //   tv_swiglu_fwd         h = bf16(silu(x1) x2), u = [x1 | x2]
 //   tv_swiglu_bwd         du1 = bf16(dh x2 s (1 + x1 (1 - s))), du2 = bf16(dh silu(x1)), s = sigmoid(x1)
 //
 // Every sum that crosses rows is taken in a fixed order through scratch partials and written: no atomics, the same bits on every
-// run.  tv_adaln_rms_bwd: per wave its 16 rows of a 64-row slab in order, the four waves in order, the slabs of a sample in order
-// (that is S), then for dw sixteen sample lanes (sample b in lane b % 16, in order) and the lanes in order.  tv_qknorm_rope_bwd: a head
-// vector is eight lanes; per lane group its vectors in pass order, the 32 groups of a block in order, then 64 block lanes (block
-// k in lane k % 64, in order) and the lanes in order.
+// run.  tv_qknorm_rope_bwd: a head vector is eight lanes; per lane group its vectors in pass order, the 32 groups of a block in order,
+// then 64 block lanes (block k in lane k % 64, in order) and the lanes in order.
 //
 // Algorithmic bytes per call (what tools/lightning_dit_bench.py divides by kernel time), T = B N rows:
-//   tv_adaln_rms_fwd  4 T C     tv_adaln_rms_bwd  6 T C (8 T C with dres)     tv_qknorm_rope_fwd  8 T C in place (12 T C out of place)
-//   tv_qknorm_rope_bwd  12 T C  tv_swiglu_fwd  6 T Hp                         tv_swiglu_bwd  10 T Hp
+//   tv_qknorm_rope_fwd  8 T C in place (12 T C out of place)     tv_qknorm_rope_bwd  12 T C
+//   tv_swiglu_fwd  6 T Hp                                        tv_swiglu_bwd  10 T Hp
 #include "common.h"
 
 #include <math.h>
@@ -28,194 +23,9 @@
 
 namespace {
 
-constexpr int LR_RPB = 64;          // rows of one sample per block (4 waves x 16 rows)
-constexpr int LR_MAX_C = 1536;      // 3 chunks per lane; the backward's LDS is 32 C bytes
-constexpr int LR_DW_LANES = 16;     // sample lanes of the dw sum
 constexpr int QK_GROUPS = 32;       // head vectors per block pass (256 threads / 8 lanes)
 constexpr int QK_MAX_BLOCKS = 1024;
 constexpr int QK_FIN_LANES = 64;    // block lanes of the dwq / dwk finalise
-
-template <int KCH>
-struct RmsRow {
-    float v[KCH][8];   // x, then xhat (0 in the lanes past the row)
-    float rstd;
-};
-
-// the statistic of one row held by a wave: one fma chain per lane over its elements, a butterfly, no mean
-template <int KCH>
-__device__ __forceinline__ void rms_load_row(const bf16* __restrict__ xr, int lane, int nch, float inv_c, float eps, RmsRow<KCH>& r) {
-    float sv = 0.f;
-#pragma unroll
-    for (int k = 0; k < KCH; ++k) {
-        const int ch = lane + 64 * k;
-        bf16x8 t = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (ch < nch) t = *(const bf16x8*)(xr + ch * 8);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            r.v[k][e] = (float)t[e];
-            sv = fmaf(r.v[k][e], r.v[k][e], sv);
-        }
-    }
-    r.rstd = rsqrtf(tv_wave_sum(sv) * inv_c + eps);
-#pragma unroll
-    for (int k = 0; k < KCH; ++k)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) r.v[k][e] *= r.rstd;
-}
-
-template <int KCH>
-__global__ __launch_bounds__(256) void adaln_rms_fwd_kernel(const bf16* __restrict__ x, const float* __restrict__ w, const float* __restrict__ mod,
-                                                            int shift_off, int scale_off, int ld, bf16* __restrict__ y, int N, int C, float eps) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nch = C >> 3, b = blockIdx.y;
-    const float inv_c = 1.0f / (float)C;
-    const float* __restrict__ mb = mod + (size_t)b * ld;
-    float sc1[KCH][8], sh[KCH][8], wv[KCH][8];
-#pragma unroll
-    for (int k = 0; k < KCH; ++k) {
-        const int ch = lane + 64 * k;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            sc1[k][e] = (ch < nch) ? 1.0f + mb[scale_off + ch * 8 + e] : 0.f;
-            sh[k][e] = (ch < nch) ? mb[shift_off + ch * 8 + e] : 0.f;
-            wv[k][e] = (ch < nch) ? w[ch * 8 + e] : 0.f;
-        }
-    }
-    const int r0 = blockIdx.x * LR_RPB, r1 = min(N, r0 + LR_RPB);
-    for (int n = r0 + wave; n < r1; n += 4) {                // (wave-uniform)
-        const size_t row = (size_t)b * N + n;
-        RmsRow<KCH> r;
-        rms_load_row<KCH>(x + row * C, lane, nch, inv_c, eps, r);
-#pragma unroll
-        for (int k = 0; k < KCH; ++k) {
-            const int ch = lane + 64 * k;
-            if (ch < nch) {
-                bf16x8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = (bf16)fmaf(r.v[k][e] * wv[k][e], sc1[k][e], sh[k][e]);
-                *(bf16x8*)(y + row * C + ch * 8) = o;
-            }
-        }
-    }
-}
-
-template <int KCH>
-__global__ __launch_bounds__(256) void adaln_rms_bwd_kernel(const bf16* __restrict__ x, const float* __restrict__ w, const float* __restrict__ mod,
-                                                            int scale_off, int ld, const bf16* __restrict__ dy, const bf16* __restrict__ dres,
-                                                            bf16* __restrict__ dx, float* __restrict__ part, int N, int C, float eps) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* s_acc = (float*)smem;      // [4 waves][2][C]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nch = C >> 3, b = blockIdx.y;
-    const float inv_c = 1.0f / (float)C;
-    const float* __restrict__ mb = mod + (size_t)b * ld;
-    float gw[KCH][8], ds[KCH][8], dq[KCH][8];
-#pragma unroll
-    for (int k = 0; k < KCH; ++k) {
-        const int ch = lane + 64 * k;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            gw[k][e] = (ch < nch) ? (1.0f + mb[scale_off + ch * 8 + e]) * w[ch * 8 + e] : 0.f;
-            ds[k][e] = dq[k][e] = 0.f;
-        }
-    }
-    const int r0 = blockIdx.x * LR_RPB, r1 = min(N, r0 + LR_RPB);
-    for (int n = r0 + wave; n < r1; n += 4) {                // (wave-uniform)
-        const size_t row = (size_t)b * N + n;
-        RmsRow<KCH> r;
-        rms_load_row<KCH>(x + row * C, lane, nch, inv_c, eps, r);
-        float g[KCH][8];
-        float a2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < KCH; ++k) {
-            const int ch = lane + 64 * k;
-            bf16x8 u = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (ch < nch) u = *(const bf16x8*)(dy + row * C + ch * 8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float d = (float)u[e];
-                g[k][e] = d * gw[k][e];
-                a2 = fmaf(g[k][e], r.v[k][e], a2);
-                ds[k][e] += d;
-                dq[k][e] = fmaf(d, r.v[k][e], dq[k][e]);
-            }
-        }
-        a2 = tv_wave_sum(a2) * inv_c;
-#pragma unroll
-        for (int k = 0; k < KCH; ++k) {
-            const int ch = lane + 64 * k;
-            if (ch < nch) {
-                bf16x8 rv = {0, 0, 0, 0, 0, 0, 0, 0};
-                if (dres) rv = *(const bf16x8*)(dres + row * C + ch * 8);
-                bf16x8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = (bf16)(r.rstd * fmaf(-r.v[k][e], a2, g[k][e]) + (float)rv[e]);
-                *(bf16x8*)(dx + row * C + ch * 8) = o;
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < KCH; ++k) {
-        const int ch = lane + 64 * k;
-        if (ch < nch) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                s_acc[(wave * 2 + 0) * C + ch * 8 + e] = ds[k][e];
-                s_acc[(wave * 2 + 1) * C + ch * 8 + e] = dq[k][e];
-            }
-        }
-    }
-    __syncthreads();
-    float* __restrict__ dst = part + ((size_t)b * gridDim.x + blockIdx.x) * 2 * C;
-    for (int i = threadIdx.x; i < 2 * C; i += 256) {
-        float a = 0.f;
-#pragma unroll
-        for (int wv = 0; wv < 4; ++wv) a += s_acc[wv * 2 * C + i];
-        dst[i] = a;
-    }
-}
-
-// dshift[b][c] = sum over the slabs of part[b][slab][0][c]; S = the same of set 1: dscale[b][c] = w[c] S, and S is kept in
-// sums[b][c] for the dw pass
-__global__ __launch_bounds__(256) void rms_mod_finalize_kernel(const float* __restrict__ part, const float* __restrict__ w, float* __restrict__ out,
-                                                               float* __restrict__ sums, int nblk, int C, int ld, int shift_off, int scale_off) {
-    const int b = blockIdx.y;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int n = 2 * C;
-    if (i >= n) return;
-    const float* __restrict__ src = part + (size_t)b * nblk * n + i;
-    float a = 0.f;
-    for (int k = 0; k < nblk; ++k) a += src[(size_t)k * n];
-    if (i < C) {
-        out[(size_t)b * ld + shift_off + i] = a;
-    } else {
-        const int c = i - C;
-        out[(size_t)b * ld + scale_off + c] = w[c] * a;
-        sums[(size_t)b * C + c] = a;
-    }
-}
-
-// dw[c] = sum_b fma(1 + scale[b][c], S[b][c], .): sample b in lane b % 16 in order, then the sixteen lanes in order.  A block is 16
-// columns x 16 sample lanes, so that the B / 16 dependent steps of a lane (not B of them) bound the launch.
-__global__ __launch_bounds__(256) void rms_dw_kernel(const float* __restrict__ sums, const float* __restrict__ mod, int scale_off, int ld,
-                                                     float* __restrict__ dw, int B, int C) {
-    __shared__ float s_acc[LR_DW_LANES][16];
-    const int col = threadIdx.x & 15, bl = threadIdx.x >> 4;
-    const int c = blockIdx.x * 16 + col;
-    float a = 0.f;
-    if (c < C) {
-#pragma unroll 4
-        for (int b = bl; b < B; b += LR_DW_LANES) a = fmaf(1.0f + mod[(size_t)b * ld + scale_off + c], sums[(size_t)b * C + c], a);
-    }
-    s_acc[bl][col] = a;
-    __syncthreads();
-    if (bl == 0 && c < C) {
-        float t = 0.f;
-#pragma unroll
-        for (int i = 0; i < LR_DW_LANES; ++i) t += s_acc[i][col];
-        dw[c] = t;
-    }
-}
 
 // ---- per-head RMSNorm of q and k with the 2-D RoPE ----------------------------------------------------------------------------
 __device__ __forceinline__ float group8_sum(float v) {
@@ -402,16 +212,6 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const bf16* __restrict_
     }
 }
 
-int lr_check(const char* name, int B, int N, int C, int ld) {
-    if (B <= 0 || N <= 0 || C <= 0 || C % 8 != 0 || C > LR_MAX_C || ld < C || B > 65535 || (long long)B * N >= (1ll << 31)) {
-        tv_set_error("%s: bad shape B=%d N=%d C=%d ld=%d (C %% 8 == 0, C <= %d, ld >= C, B <= 65535, B N < 2^31)", name, B, N, C, ld, LR_MAX_C);
-        return TV_ERR_ARG;
-    }
-    return TV_OK;
-}
-
-bool lr_range(int off, int C, int ld) { return off >= 0 && (long long)off + C <= ld; }
-
 int qk_check(const char* name, int B, int N, int heads) {
     if (B <= 0 || N <= 0 || heads <= 0 || (long long)B * N * 3 * heads >= (1ll << 31)) {
         tv_set_error("%s: bad shape B=%d N=%d heads=%d (positive, B N 3 heads < 2^31)", name, B, N, heads);
@@ -439,51 +239,6 @@ unsigned sw_blocks(long long total) {
 }
 
 }  // namespace
-
-extern "C" int tv_adaln_rms_fwd(const void* x, const float* w, const float* mod, int shift_off, int scale_off, int ld, void* y, int B, int N, int C,
-                                float eps, void* stream) {
-    if (lr_check("tv_adaln_rms_fwd", B, N, C, ld)) return TV_ERR_ARG;
-    TV_CHECK_ARG(x && w && mod && y, "tv_adaln_rms_fwd: null pointer");
-    TV_CHECK_ARG(lr_range(shift_off, C, ld) && lr_range(scale_off, C, ld), "tv_adaln_rms_fwd: column ranges %d / %d + %d outside ld=%d", shift_off,
-                 scale_off, C, ld);
-    TV_CHECK_ARG((((uintptr_t)x | (uintptr_t)y) & 15) == 0, "tv_adaln_rms_fwd: x / y must be 16-byte aligned");
-    const dim3 grid(tv_cdiv(N, LR_RPB), B);
-    const int kch = tv_cdiv(C >> 3, 64);
-#define TV_LR_FWD(K) hipLaunchKernelGGL(adaln_rms_fwd_kernel<K>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16*)x, w, mod, shift_off, scale_off, ld, (bf16*)y, N, C, eps)
-    if (kch <= 1) TV_LR_FWD(1); else if (kch == 2) TV_LR_FWD(2); else TV_LR_FWD(3);
-#undef TV_LR_FWD
-    TV_CHECK_LAUNCH("tv_adaln_rms_fwd");
-    return TV_OK;
-}
-
-extern "C" long long tv_adaln_rms_bwd_partial_count(int B, int N, int C) {
-    if (B <= 0 || N <= 0 || C <= 0) return -1;
-    return (long long)B * tv_cdiv(N, LR_RPB) * 2 * C + (long long)B * C;          // floats: the slab partials, then S
-}
-
-extern "C" int tv_adaln_rms_bwd(const void* x, const float* w, const float* mod, int shift_off, int scale_off, int ld, const void* dy, const void* dres,
-                                void* dx, float* dmod, float* dw, float* partials, int B, int N, int C, float eps, void* stream) {
-    if (lr_check("tv_adaln_rms_bwd", B, N, C, ld)) return TV_ERR_ARG;
-    TV_CHECK_ARG(x && w && mod && dy && dx && dmod && dw && partials, "tv_adaln_rms_bwd: null pointer");
-    TV_CHECK_ARG(lr_range(shift_off, C, ld) && lr_range(scale_off, C, ld) && (shift_off + C <= scale_off || scale_off + C <= shift_off),
-                 "tv_adaln_rms_bwd: column ranges %d / %d + %d outside ld=%d or overlapping", shift_off, scale_off, C, ld);
-    TV_CHECK_ARG((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dres | (uintptr_t)dx) & 15) == 0, "tv_adaln_rms_bwd: x / dy / dres / dx must be 16-byte aligned");
-    const int nblk = tv_cdiv(N, LR_RPB);
-    const dim3 grid(nblk, B);
-    const int kch = tv_cdiv(C >> 3, 64);
-    const size_t lds = (size_t)8 * C * sizeof(float);
-    float* sums = partials + (size_t)B * nblk * 2 * C;
-#define TV_LR_BWD(K) hipLaunchKernelGGL(adaln_rms_bwd_kernel<K>, grid, dim3(256), lds, (hipStream_t)stream, (const bf16*)x, w, mod, scale_off, ld, (const bf16*)dy, (const bf16*)dres, (bf16*)dx, partials, N, C, eps)
-    if (kch <= 1) TV_LR_BWD(1); else if (kch == 2) TV_LR_BWD(2); else TV_LR_BWD(3);
-#undef TV_LR_BWD
-    TV_CHECK_LAUNCH("tv_adaln_rms_bwd");
-    hipLaunchKernelGGL(rms_mod_finalize_kernel, dim3(tv_cdiv(2 * C, 256), B), dim3(256), 0, (hipStream_t)stream, (const float*)partials, w, dmod, sums, nblk, C,
-                       ld, shift_off, scale_off);
-    TV_CHECK_LAUNCH("tv_adaln_rms_bwd (finalise)");
-    hipLaunchKernelGGL(rms_dw_kernel, dim3(tv_cdiv(C, 16)), dim3(256), 0, (hipStream_t)stream, (const float*)sums, mod, scale_off, ld, dw, B, C);
-    TV_CHECK_LAUNCH("tv_adaln_rms_bwd (dw)");
-    return TV_OK;
-}
 
 extern "C" int tv_qknorm_rope_fwd(const void* qkv, const float* wq, const float* wk, const float* rope_tab, void* out, int B, int N, int heads, float eps,
                                   void* stream) {

@@ -8,7 +8,7 @@
 // them to its own row of a partials buffer; a finalize kernel adds the rows in a fixed order into
 // the [B][C][2] fp32 result (no atomics: bit-reproducible); groups are folded from channels by
 // the consumer.  The same reduction skeleton serves the backward sums.
-#include "common.h"
+#include "row_wave.h"
 
 namespace {
 
@@ -341,31 +341,11 @@ __global__ __launch_bounds__(256) void rownorm_fwd_kernel(const bf16* __restrict
     const int nch = C >> 3;
     const float inv_c = 1.0f / (float)C;
     float wv[KCH][8];
-    if constexpr (MODE == 1) {
-#pragma unroll
-        for (int k = 0; k < KCH; ++k) {
-            const int ch = lane + 64 * k;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) wv[k][e] = (ch < nch) ? w[ch * 8 + e] : 0.f;
-        }
-    }
+    if constexpr (MODE == 1) rw_load_cols<KCH>(w, lane, nch, 0.f, wv);
     for (int row = blockIdx.x * 4 + wave; row < T; row += gridDim.x * 4) {
-        const bf16* xr = x + (size_t)row * C;
         float v[KCH][8];
-        float ss = 0.f;
-#pragma unroll
-        for (int k = 0; k < KCH; ++k) {
-            const int ch = lane + 64 * k;
-            bf16x8 t = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (ch < nch) t = *(const bf16x8*)(xr + ch * 8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                v[k][e] = (float)t[e];
-                ss = fmaf(v[k][e], v[k][e], ss);
-            }
-        }
-        ss = tv_wave_sum(ss);
-        const float r = rsqrtf(ss * inv_c + eps_rms);
+        rw_load<KCH>(x + (size_t)row * C, lane, nch, v);
+        const float r = rsqrtf(rw_sumsq<KCH>(v) * inv_c + eps_rms);
         float mu = 0.f, s = 1.f;
         if constexpr (MODE == 1) {
             float su = 0.f;
@@ -391,17 +371,8 @@ __global__ __launch_bounds__(256) void rownorm_fwd_kernel(const bf16* __restrict
             }
             s = rsqrtf(tv_wave_sum(sv) * inv_c + eps_ln);
         }
-        bf16* yr = y + (size_t)row * C;
-#pragma unroll
-        for (int k = 0; k < KCH; ++k) {
-            const int ch = lane + 64 * k;
-            if (ch < nch) {
-                bf16x8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = (MODE == 1) ? (bf16)((v[k][e] - mu) * s) : (bf16)(v[k][e] * r);
-                *(bf16x8*)(yr + ch * 8) = o;
-            }
-        }
+        rw_store<KCH>(y, nullptr, (size_t)row * C, lane, nch,
+                      [&](int k, int e, float) { return (MODE == 1) ? (v[k][e] - mu) * s : v[k][e] * r; });
     }
 }
 
@@ -418,6 +389,8 @@ __global__ __launch_bounds__(256) void rownorm_bwd_kernel(const bf16* __restrict
     float wv[KCH][8], dwv[KCH][8];
     if constexpr (MODE == 1) {
         for (int i = threadIdx.x; i < C; i += 256) s_dw[i] = 0.f;
+        // (not rw_load_cols: on its wider loads of w the compiler packs xhat w into v_pk_mul_f32 and stops contracting
+        // `su += xhat w` below, which moves the bits of dx)
 #pragma unroll
         for (int k = 0; k < KCH; ++k) {
             const int ch = lane + 64 * k;
@@ -430,27 +403,10 @@ __global__ __launch_bounds__(256) void rownorm_bwd_kernel(const bf16* __restrict
         __syncthreads();
     }
     for (int row = blockIdx.x * 4 + wave; row < T; row += gridDim.x * 4) {
-        const bf16* xr = x + (size_t)row * C;
-        const bf16* gr = dy + (size_t)row * C;
         float xh[KCH][8], g[KCH][8];
-        float ss = 0.f;
-#pragma unroll
-        for (int k = 0; k < KCH; ++k) {
-            const int ch = lane + 64 * k;
-            bf16x8 t = {0, 0, 0, 0, 0, 0, 0, 0}, u = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (ch < nch) {
-                t = *(const bf16x8*)(xr + ch * 8);
-                u = *(const bf16x8*)(gr + ch * 8);
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                xh[k][e] = (float)t[e];
-                g[k][e] = (float)u[e];
-                ss = fmaf(xh[k][e], xh[k][e], ss);
-            }
-        }
-        ss = tv_wave_sum(ss);
-        const float r = rsqrtf(ss * inv_c + eps_rms);
+        rw_load<KCH>(x + (size_t)row * C, lane, nch, xh);
+        rw_load<KCH>(dy + (size_t)row * C, lane, nch, g);
+        const float r = rsqrtf(rw_sumsq<KCH>(xh) * inv_c + eps_rms);
 #pragma unroll
         for (int k = 0; k < KCH; ++k)
 #pragma unroll
@@ -510,19 +466,7 @@ __global__ __launch_bounds__(256) void rownorm_bwd_kernel(const bf16* __restrict
 #pragma unroll
             for (int e = 0; e < 8; ++e) a3 = fmaf(g[k][e], xh[k][e], a3);
         a3 = tv_wave_sum(a3) * inv_c;
-        bf16* dr = dx + (size_t)row * C;
-#pragma unroll
-        for (int k = 0; k < KCH; ++k) {
-            const int ch = lane + 64 * k;
-            if (ch < nch) {
-                bf16x8 rv = {0, 0, 0, 0, 0, 0, 0, 0};
-                if (dres) rv = *(const bf16x8*)(dres + (size_t)row * C + ch * 8);
-                bf16x8 o;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = (bf16)(r * (g[k][e] - xh[k][e] * a3) + (float)rv[e]);
-                *(bf16x8*)(dr + ch * 8) = o;
-            }
-        }
+        rw_store<KCH>(dx, dres, (size_t)row * C, lane, nch, [&](int k, int e, float res) { return r * (g[k][e] - xh[k][e] * a3) + res; });
     }
     if constexpr (MODE == 1) {
 #pragma unroll
@@ -558,37 +502,15 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const bf16* __restr
             const int b = row / per;
             src = b * n_tok + skip + (row - b * per);
         }
-        const bf16* xr = x + (size_t)src * C;
         float v[KCH][8];
-        float su = 0.f;
+        rw_load<KCH>(x + (size_t)src * C, lane, nch, v);
+        const float mu = rw_sum<KCH>(v) * inv_c;
+        const float s = rsqrtf(rw_centre<KCH>(v, lane, nch, mu) * inv_c + eps);
+        if constexpr (FINAL) {
 #pragma unroll
-        for (int k = 0; k < KCH; ++k) {
-            const int ch = lane + 64 * k;
-            bf16x8 t = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (ch < nch) t = *(const bf16x8*)(xr + ch * 8);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                v[k][e] = (float)t[e];
-                su += v[k][e];
-            }
-        }
-        const float mu = tv_wave_sum(su) * inv_c;
-        float sv = 0.f;
-#pragma unroll
-        for (int k = 0; k < KCH; ++k) {
-            const int ch = lane + 64 * k;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                v[k][e] = (ch < nch) ? v[k][e] - mu : 0.f;
-                sv = fmaf(v[k][e], v[k][e], sv);
-            }
-        }
-        const float s = rsqrtf(tv_wave_sum(sv) * inv_c + eps);
-#pragma unroll
-        for (int k = 0; k < KCH; ++k) {
-            const int ch = lane + 64 * k;
-            if (ch < nch) {
-                if constexpr (FINAL) {
+            for (int k = 0; k < KCH; ++k) {
+                const int ch = lane + 64 * k;
+                if (ch < nch) {
                     float* yr = y32 + (size_t)row * C + ch * 8;
                     const f32x4 g0 = *(const f32x4*)(gamma + ch * 8), g1 = *(const f32x4*)(gamma + ch * 8 + 4);
                     const f32x4 b0 = *(const f32x4*)(beta + ch * 8), b1 = *(const f32x4*)(beta + ch * 8 + 4);
@@ -600,13 +522,10 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const bf16* __restr
                     }
                     *(f32x4*)yr = o0;
                     *(f32x4*)(yr + 4) = o1;
-                } else {
-                    bf16x8 o;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) o[e] = (bf16)(v[k][e] * s);
-                    *(bf16x8*)(y16 + (size_t)row * C + ch * 8) = o;
                 }
             }
+        } else {
+            rw_store<KCH>(y16, nullptr, (size_t)row * C, lane, nch, [&](int k, int e, float) { return v[k][e] * s; });
         }
     }
 }
@@ -709,21 +628,16 @@ extern "C" int tv_rownorm_fwd(const void* x, const float* w, void* y, int T, int
     TV_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 64 * 8 * RN_MAXCH, "tv_rownorm_fwd: C=%d must be a multiple of 8 and <= 2560", C);
     TV_CHECK_ARG(mode == 0 || (mode == 1 && w) || mode == 2, "tv_rownorm_fwd: mode %d (mode 1 needs w)", mode);
     const int grid = min(tv_cdiv(T, 4), 256 * 8);
-    const int kch = tv_cdiv(C >> 3, 64);      // 16-byte chunks per lane
-    if (mode == 2) {
-#define TV_LN_FWD(K) hipLaunchKernelGGL((layernorm_rows_kernel<K, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, nullptr, nullptr, (bf16*)y, nullptr, T, C, 1, 0, eps_ln)
-        if (kch <= 1) TV_LN_FWD(1); else if (kch == 2) TV_LN_FWD(2); else if (kch == 3) TV_LN_FWD(3); else TV_LN_FWD(5);
-#undef TV_LN_FWD
-        TV_CHECK_LAUNCH("tv_rownorm_fwd");
-        return TV_OK;
-    }
-#define TV_RN_FWD(M, K) hipLaunchKernelGGL((rownorm_fwd_kernel<M, K>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, w, (bf16*)y, T, C, eps_rms, eps_ln)
-    if (mode == 0) {
-        if (kch <= 1) TV_RN_FWD(0, 1); else if (kch == 2) TV_RN_FWD(0, 2); else if (kch == 3) TV_RN_FWD(0, 3); else TV_RN_FWD(0, 5);
-    } else {
-        if (kch <= 1) TV_RN_FWD(1, 1); else if (kch == 2) TV_RN_FWD(1, 2); else if (kch == 3) TV_RN_FWD(1, 3); else TV_RN_FWD(1, 5);
-    }
-#undef TV_RN_FWD
+    rw_dispatch<1, 2, 3, 5>(tv_cdiv(C >> 3, 64), [&](auto K) {      // 16-byte chunks per lane
+        constexpr int kch = decltype(K)::value;
+        if (mode == 2)
+            hipLaunchKernelGGL((layernorm_rows_kernel<kch, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, nullptr, nullptr,
+                               (bf16*)y, nullptr, T, C, 1, 0, eps_ln);
+        else if (mode == 0)
+            hipLaunchKernelGGL((rownorm_fwd_kernel<0, kch>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, w, (bf16*)y, T, C, eps_rms, eps_ln);
+        else
+            hipLaunchKernelGGL((rownorm_fwd_kernel<1, kch>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, w, (bf16*)y, T, C, eps_rms, eps_ln);
+    });
     TV_CHECK_LAUNCH("tv_rownorm_fwd");
     return TV_OK;
 }
@@ -736,10 +650,10 @@ extern "C" int tv_layernorm_rows(const void* x, const float* gamma, const float*
     TV_CHECK_ARG((long long)B * n_tok < (1ll << 31), "tv_layernorm_rows: too many rows");
     const int T = B * (n_tok - skip);
     const int grid = min(tv_cdiv(T, 4), 256 * 8);
-    const int kch = tv_cdiv(C >> 3, 64);
-#define TV_LN_FIN(K) hipLaunchKernelGGL((layernorm_rows_kernel<K, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, gamma, beta, nullptr, y, T, C, n_tok, skip, eps)
-    if (kch <= 1) TV_LN_FIN(1); else if (kch == 2) TV_LN_FIN(2); else if (kch == 3) TV_LN_FIN(3); else TV_LN_FIN(5);
-#undef TV_LN_FIN
+    rw_dispatch<1, 2, 3, 5>(tv_cdiv(C >> 3, 64), [&](auto K) {
+        hipLaunchKernelGGL((layernorm_rows_kernel<decltype(K)::value, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, gamma, beta,
+                           nullptr, y, T, C, n_tok, skip, eps);
+    });
     TV_CHECK_LAUNCH("tv_layernorm_rows");
     return TV_OK;
 }
@@ -750,15 +664,15 @@ extern "C" int tv_rownorm_bwd(const void* x, const float* w, const void* dy, con
     TV_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 64 * 8 * RN_MAXCH, "tv_rownorm_bwd: C=%d must be a multiple of 8 and <= 2560", C);
     TV_CHECK_ARG(mode == 0 || (mode == 1 && w && dw), "tv_rownorm_bwd: mode %d (mode 1 needs w and dw)", mode);
     const int grid = min(tv_cdiv(T, 4), 256 * 4);
-    const int kch = tv_cdiv(C >> 3, 64);      // 16-byte chunks per lane
-#define TV_RN_BWD(M, K) hipLaunchKernelGGL((rownorm_bwd_kernel<M, K>), dim3(grid), dim3(256), (M) ? C * sizeof(float) : 0, (hipStream_t)stream, \
-                                           (const bf16*)x, w, (const bf16*)dy, (const bf16*)dres, (bf16*)dx, dw, T, C, eps_rms, eps_ln)
-    if (mode == 0) {
-        if (kch <= 1) TV_RN_BWD(0, 1); else if (kch == 2) TV_RN_BWD(0, 2); else if (kch == 3) TV_RN_BWD(0, 3); else TV_RN_BWD(0, 5);
-    } else {
-        if (kch <= 1) TV_RN_BWD(1, 1); else if (kch == 2) TV_RN_BWD(1, 2); else if (kch == 3) TV_RN_BWD(1, 3); else TV_RN_BWD(1, 5);
-    }
-#undef TV_RN_BWD
+    rw_dispatch<1, 2, 3, 5>(tv_cdiv(C >> 3, 64), [&](auto K) {      // 16-byte chunks per lane
+        constexpr int kch = decltype(K)::value;
+        if (mode == 0)
+            hipLaunchKernelGGL((rownorm_bwd_kernel<0, kch>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, w, (const bf16*)dy,
+                               (const bf16*)dres, (bf16*)dx, dw, T, C, eps_rms, eps_ln);
+        else
+            hipLaunchKernelGGL((rownorm_bwd_kernel<1, kch>), dim3(grid), dim3(256), C * sizeof(float), (hipStream_t)stream, (const bf16*)x, w, (const bf16*)dy,
+                               (const bf16*)dres, (bf16*)dx, dw, T, C, eps_rms, eps_ln);
+    });
     TV_CHECK_LAUNCH("tv_rownorm_bwd");
     return TV_OK;
 }

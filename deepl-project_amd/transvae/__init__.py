@@ -30,7 +30,7 @@ integrate the velocity field with Euler steps and classifier-free guidance and d
 (transvae/evaluate_dit.py, transvae/metrics_gen.py, csrc/genmetrics.hip): `evaluate_dit` samples, extracts Inception features and
 returns gFID, Inception Score (`InceptionScore`) and the k-NN precision / recall (`knn_radius`, `manifold_hits`,
 `precision_recall`) against a `reference_statistics` dict; `ParamEMA` (transvae/optim.py) is the weight average they are measured on,
-kept by `fit_dit(..., ema_decay=...)`.  `LightningDiT` / `create_lightning_dit` (transvae/lightning_dit.py, csrc/lightning.hip)
+kept by `fit_dit(..., ema_decay=...)`.  `LightningDiT` / `create_lightning_dit` (transvae/lightning_dit.py, csrc/lightning.hip, csrc/dit.hip)
 are the same model with the LightningDiT block: RMSNorm adaLN with a learned weight, per-head qk-norm before the RoPE and a SwiGLU MLP,
 each behind a switch; the training, sampling and evaluation entry points above take it unchanged.
 """

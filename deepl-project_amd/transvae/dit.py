@@ -68,38 +68,50 @@ def _check_rows(x: torch.Tensor, mod: torch.Tensor, N: int, what: str):
 
 
 class _AdaLNFn(torch.autograd.Function):
+    """`adaln` (w = None: the LayerNorm entry points, no weight gradient) and `lightning_dit.adaln_rms` (the RMSNorm's fp32 weight)."""
+
     @staticmethod
-    def forward(ctx, x, mod, shift_off, scale_off, N, eps, sink, owner):
-        _check_rows(x, mod, N, "adaln")
+    def forward(ctx, x, w, mod, shift_off, scale_off, N, eps, sink, owner):
         B, ld = mod.shape
+        lib = L.load()
         y = torch.empty_like(x)
-        L.check(L.load().tv_adaln_fwd(ops._p(x), ops._p(mod), shift_off, scale_off, ld, ops._p(y), B, N, x.shape[1], eps, ops._stream()),
-                "tv_adaln_fwd")
+        tail = (ops._p(mod), shift_off, scale_off, ld, ops._p(y), B, N, x.shape[1], eps, ops._stream())
+        if w is None:
+            L.check(lib.tv_adaln_fwd(ops._p(x), *tail), "tv_adaln_fwd")
+        else:
+            L.check(lib.tv_adaln_rms_fwd(ops._p(x), ops._p(w), *tail), "tv_adaln_rms_fwd")
         ctx.args = (shift_off, scale_off, N, eps, sink, owner)
-        ctx.save_for_backward(x, mod)
+        ctx.save_for_backward(x, w, mod)
         return y, x            # the second output is the residual stream itself: its gradient comes back as `dres`
 
     @staticmethod
     def backward(ctx, gy, gres):
-        x, mod = ctx.saved_tensors
+        x, w, mod = ctx.saved_tensors
         shift_off, scale_off, N, eps, sink, owner = ctx.args
+        what = "adaln" if w is None else "adaln_rms"
         B, ld = mod.shape
         C = x.shape[1]
         lib = L.load()
         gy = gy.contiguous()
         if gres is not None:
             gres = gres.contiguous()
-            ops._require(gres.dtype == torch.bfloat16, "adaln: the residual stream's gradient must be bf16")
-        ops._require(gy.dtype == torch.bfloat16, "adaln: bf16 gradient rows")
+            ops._require(gres.dtype == torch.bfloat16, f"{what}: the residual stream's gradient must be bf16")
+        ops._require(gy.dtype == torch.bfloat16, f"{what}: bf16 gradient rows")
         dx = torch.empty_like(x)
+        dw = None if w is None else torch.empty_like(w)
         dmod = sink.buffer(mod) if sink is not None else torch.zeros_like(mod)
-        part = torch.empty(lib.tv_adaln_bwd_partial_count(B, N, C), dtype=torch.float32, device=x.device)
-        L.check(lib.tv_adaln_bwd(ops._p(x), ops._p(mod), shift_off, scale_off, ld, ops._p(gy), ops._p(gres), ops._p(dx), ops._p(dmod), ops._p(part),
-                                 B, N, C, eps, ops._stream()), "tv_adaln_bwd")
+        count = lib.tv_adaln_bwd_partial_count if w is None else lib.tv_adaln_rms_bwd_partial_count
+        part = torch.empty(count(B, N, C), dtype=torch.float32, device=x.device)
+        head = (ops._p(mod), shift_off, scale_off, ld, ops._p(gy), ops._p(gres), ops._p(dx), ops._p(dmod))
+        tail = (ops._p(part), B, N, C, eps, ops._stream())
+        if w is None:
+            L.check(lib.tv_adaln_bwd(ops._p(x), *head, *tail), "tv_adaln_bwd")
+        else:
+            L.check(lib.tv_adaln_rms_bwd(ops._p(x), ops._p(w), *head, ops._p(dw), *tail), "tv_adaln_rms_bwd")
         if sink is not None:
             sink.filled += 2
             dmod = sink.take() if owner else None
-        return dx, dmod, None, None, None, None, None, None
+        return dx, dw, dmod, None, None, None, None, None, None
 
 
 class _GateResidualFn(torch.autograd.Function):
@@ -140,7 +152,8 @@ def adaln(x: torch.Tensor, mod: torch.Tensor, shift_off: int, scale_off: int, to
     """(LN-hat(x) (1 + scale) + shift, x): bf16 rows [B tokens, C]; shift / scale are C columns of the fp32 `mod` [B, ld] from the
     given offsets.  The second result IS x; feed it to `gate_residual` so that the residual stream's gradient joins the LayerNorm
     backward in fp32 inside the kernel.  Without a `sink` the backward returns a full gradient of `mod` with its two ranges filled."""
-    return _AdaLNFn.apply(x, mod, int(shift_off), int(scale_off), int(tokens), float(eps), sink, bool(owner))
+    _check_rows(x, mod, int(tokens), "adaln")
+    return _AdaLNFn.apply(x, None, mod, int(shift_off), int(scale_off), int(tokens), float(eps), sink, bool(owner))
 
 
 def gate_residual(x: torch.Tensor, y: torch.Tensor, mod: torch.Tensor, gate_off: int, tokens: int, sink: Optional[ModGrad] = None) -> torch.Tensor:

@@ -7,9 +7,10 @@ a TODO there).  `LightningDiT` is `DiT` with three switches, each of which repla
     use_qknorm    per-head RMSNorm of q and k before the 2-D RoPE                                   `qk_norm_rope_attention`
     use_swiglu    w3(silu(x1) x2), [x1 | x2] = w12(x), inner width (2 int(C mlp_ratio)) // 3         `swiglu`
 
-The three kernel pairs are csrc/lightning.hip; everything else (embedders, conditioning path, padding, RoPE table, token GEMMs,
-attention, gate + residual, the flow-matching edge, `flow_matching_loss` / `sample_latents` / `fit_dit` / `evaluate_dit`) is what
-`DiT` uses, unchanged.  With a switch off that part of the block is the DiT path.  There is no CPU fallback: host tensors raise.
+`adaln_rms` is the RMS form of the adaLN kernel pair in csrc/dit.hip, the other two pairs are csrc/lightning.hip; everything else
+(embedders, conditioning path, padding, RoPE table, token GEMMs, attention, gate + residual, the flow-matching edge,
+`flow_matching_loss` / `sample_latents` / `fit_dit` / `evaluate_dit`) is what `DiT` uses, unchanged.  With a switch off that part of the
+block is the DiT path.  There is no CPU fallback: host tensors raise.
 """
 from __future__ import annotations
 
@@ -19,7 +20,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .dit import LN_EPS, DiT, ModGrad, _check_rows, adaln, flow_rows, gate_residual
+from .dit import LN_EPS, DiT, ModGrad, _AdaLNFn, _check_rows, adaln, flow_rows, gate_residual
 from .hip import _lib as L
 from .hip import ops
 from .probe import _round_up
@@ -34,43 +35,6 @@ def _check_weight(w: torch.Tensor, n: int, like: torch.Tensor, what: str):
     ops._need_gpu(w)
     ops._require(w.dtype == torch.float32 and tuple(w.shape) == (n,) and w.is_contiguous() and w.device == like.device,
                  f"{what}: contiguous fp32 weight [{n}] on the rows' device")
-
-
-class _AdaLNRmsFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w, mod, shift_off, scale_off, N, eps, sink, owner):
-        _check_rows(x, mod, N, "adaln_rms")
-        _check_weight(w, x.shape[1], x, "adaln_rms")
-        B, ld = mod.shape
-        y = torch.empty_like(x)
-        L.check(L.load().tv_adaln_rms_fwd(ops._p(x), ops._p(w), ops._p(mod), shift_off, scale_off, ld, ops._p(y), B, N, x.shape[1], eps,
-                                          ops._stream()), "tv_adaln_rms_fwd")
-        ctx.args = (shift_off, scale_off, N, eps, sink, owner)
-        ctx.save_for_backward(x, w, mod)
-        return y, x            # the second output is the residual stream itself: its gradient comes back as `dres`
-
-    @staticmethod
-    def backward(ctx, gy, gres):
-        x, w, mod = ctx.saved_tensors
-        shift_off, scale_off, N, eps, sink, owner = ctx.args
-        B, ld = mod.shape
-        C = x.shape[1]
-        lib = L.load()
-        gy = gy.contiguous()
-        if gres is not None:
-            gres = gres.contiguous()
-            ops._require(gres.dtype == torch.bfloat16, "adaln_rms: the residual stream's gradient must be bf16")
-        ops._require(gy.dtype == torch.bfloat16, "adaln_rms: bf16 gradient rows")
-        dx = torch.empty_like(x)
-        dw = torch.empty_like(w)
-        dmod = sink.buffer(mod) if sink is not None else torch.zeros_like(mod)
-        part = torch.empty(lib.tv_adaln_rms_bwd_partial_count(B, N, C), dtype=torch.float32, device=x.device)
-        L.check(lib.tv_adaln_rms_bwd(ops._p(x), ops._p(w), ops._p(mod), shift_off, scale_off, ld, ops._p(gy), ops._p(gres), ops._p(dx),
-                                     ops._p(dmod), ops._p(dw), ops._p(part), B, N, C, eps, ops._stream()), "tv_adaln_rms_bwd")
-        if sink is not None:
-            sink.filled += 2
-            dmod = sink.take() if owner else None
-        return dx, dw, dmod, None, None, None, None, None, None
 
 
 class _QkNormRopeAttnFn(torch.autograd.Function):
@@ -144,7 +108,9 @@ def adaln_rms(x: torch.Tensor, weight: torch.Tensor, mod: torch.Tensor, shift_of
     """(RMSNorm(x; weight) (1 + scale) + shift, x): `dit.adaln` on an RMSNorm with a learned fp32 weight [C].  bf16 rows
     [B tokens, C]; shift / scale are C columns of the fp32 `mod` [B, ld] from the given offsets; the second result IS x, and the `sink`
     / `owner` protocol is `dit.adaln`'s.  The weight's gradient is written by the same backward launch sequence, bit-reproducibly."""
-    return _AdaLNRmsFn.apply(x, weight, mod, int(shift_off), int(scale_off), int(tokens), float(eps), sink, bool(owner))
+    _check_rows(x, mod, int(tokens), "adaln_rms")
+    _check_weight(weight, x.shape[1], x, "adaln_rms")
+    return _AdaLNFn.apply(x, weight, mod, int(shift_off), int(scale_off), int(tokens), float(eps), sink, bool(owner))
 
 
 def qk_norm_rope_attention(qkv: torch.Tensor, q_weight: torch.Tensor, k_weight: torch.Tensor, rope_tab: Optional[torch.Tensor], heads: int,

@@ -373,7 +373,7 @@ def swiglu_bwd64(u, dh):
 # fp32 emulations in the kernels' own order (defect=...: the same with a named defect)
 # ---------------------------------------------------------------------------------------------------------------------------
 def _rms_stats(x, C, eps=LN_EPS, defect=None):
-    """(xhat in lane layout, rstd [T, 1]): the one-chain statistic of rms_load_row"""
+    """(xhat in lane layout, rstd [T, 1]): the one-chain statistic of ad_load_xhat<KCH, true>"""
     xl, mask = R._lanes(x.to(F32))
     inv_c = torch.tensor(1.0 / C, dtype=F32)
     if defect == "stat_bf16":                       # the sum of squares kept in bf16

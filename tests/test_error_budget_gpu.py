@@ -676,7 +676,7 @@ def test_groupnorm_rejects_bad_shapes(C, G):
 
 
 ROWNORM_LOOP = 8192 + 4 * 2048 + 13     # rows: the forward's 2048 blocks x 4 waves twice and a ragged third pass, the backward's
-                                        # 1024 x 4 four times and a ragged fifth (norm.hip:352,432)
+                                        # 1024 x 4 four times and a ragged fifth (norm.hip:345,405)
 
 
 def _rownorm_run(x, w, gy, dres, mode, dw0=None):

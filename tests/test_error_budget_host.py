@@ -1123,7 +1123,7 @@ def rownorm_dres(dx64, seed=0):
 
 
 def rownorm_fwd_emul(x, w, mode, mutate=None):
-    """fp32 in the kernel's order of operations (norm.hip:352-404): ss = sum x^2, r = rsqrt(ss / C + eps); mode 1:
+    """fp32 in the kernel's order of operations (norm.hip:345-376): ss = sum x^2, r = rsqrt(ss / C + eps); mode 1:
     u = (x r) w, mu = sum u / C, s = rsqrt(sum (u - mu)^2 / C + eps), y = bf16((u - mu) s); mode 0: y = bf16(x r).
     mutate 'u_bf16': u rounded to bf16 between the two norms."""
     xf = x.float()
@@ -1141,7 +1141,7 @@ def rownorm_fwd_emul(x, w, mode, mutate=None):
 
 
 def rownorm_bwd_emul(x, w, gy, dres, mode, mutate=None, reorder=False):
-    """fp32 in the kernel's order of operations (norm.hip:432-537) -> (dx, dw | None).  xhat = x r; mode 1: u = xhat w, mu, s
+    """fp32 in the kernel's order of operations (norm.hip:405-481) -> (dx, dw | None).  xhat = x r; mode 1: u = xhat w, mu, s
     as in the forward, y = (u - mu) s, du = s (g - mean g - y mean(g y)), dw += du xhat, g := du w; then
     dx = bf16(r (g - xhat mean(g xhat)) + dres).  The row sum of dw is in no fixed order in the kernel (per-lane chains over a
     block's rows, LDS atomics over its waves, global atomics over the blocks): `reorder` sums 37 interleaved row classes as

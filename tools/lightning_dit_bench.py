@@ -1,9 +1,9 @@
-"""Cost of the LightningDiT block (transvae.lightning_dit, csrc/lightning.hip).  GPU box.
+"""Cost of the LightningDiT block (transvae.lightning_dit; csrc/lightning.hip and the RMS adaLN of csrc/dit.hip).  GPU box.
 
     python tools/lightning_dit_bench.py [--iters 10] [--out profiles/lightning_dit_bench.json]
 
 Every GPU step runs in a fresh child process under its own `timeout`; a step that fails ends the run.  At most 16 host threads.
-1. `kernels`: device events around warmed-up loops of C-ABI calls, three windows each: the six kernels of csrc/lightning.hip at
+1. `kernels`: device events around warmed-up loops of C-ABI calls, three windows each: the block's six kernels at
               LightningDiT-B's shape (256 samples x 256 tokens x 768, 12 heads, Hp = 2048) and, in the same process, the yardstick:
               `tv_adaln_fwd` / `_bwd` and `tv_gate_residual_fwd` / `_bwd` of csrc/dit.hip at that shape.  TB/s on the algorithmic bytes
               of the files' headers (`tv_adaln_*_bwd` with `dres`, `tv_qknorm_rope_fwd` in place).
@@ -37,10 +37,10 @@ T = B * N
 BYTES = {"tv_adaln_rms_fwd": 4 * T * C_, "tv_adaln_rms_bwd": 8 * T * C_, "tv_qknorm_rope_fwd": 8 * T * C_, "tv_qknorm_rope_bwd": 12 * T * C_,
          "tv_swiglu_fwd": 6 * T * HP, "tv_swiglu_bwd": 10 * T * HP,
          "tv_adaln_fwd": 4 * T * C_, "tv_adaln_bwd": 8 * T * C_, "tv_gate_residual_fwd": 6 * T * C_, "tv_gate_residual_bwd": 6 * T * C_}
-KERNEL_OF = {"adaln_rms_fwd_kernel": "tv_adaln_rms_fwd", "adaln_rms_bwd_kernel": "tv_adaln_rms_bwd", "qknorm_rope_fwd_kernel": "tv_qknorm_rope_fwd",
+# kernel name -> C-ABI call; the adaLN pair is one template, `adaln_*_kernel<KCH, RMS>`: its `true>` instantiations are tv_adaln_rms_*
+KERNEL_OF = {"adaln_fwd_kernel": "tv_adaln_fwd", "adaln_bwd_kernel": "tv_adaln_bwd", "qknorm_rope_fwd_kernel": "tv_qknorm_rope_fwd",
              "qknorm_rope_bwd_kernel": "tv_qknorm_rope_bwd", "swiglu_fwd_kernel": "tv_swiglu_fwd", "swiglu_bwd_kernel": "tv_swiglu_bwd",
-             "adaln_fwd_kernel": "tv_adaln_fwd", "adaln_bwd_kernel": "tv_adaln_bwd", "gate_fwd_kernel": "tv_gate_residual_fwd",
-             "gate_bwd_kernel": "tv_gate_residual_bwd"}
+             "gate_fwd_kernel": "tv_gate_residual_fwd", "gate_bwd_kernel": "tv_gate_residual_bwd"}
 YARDSTICK = {"tv_adaln_rms_fwd": "tv_adaln_fwd", "tv_adaln_rms_bwd": "tv_adaln_bwd"}
 
 
@@ -229,6 +229,8 @@ def main():
                 name, avg_ns = row.get("Name", ""), float(row.get("AverageNs") or 0)
                 for k, api in KERNEL_OF.items():
                     if k in name and avg_ns:
+                        if k.startswith("adaln_") and "true>" in name:
+                            api = api.replace("tv_adaln_", "tv_adaln_rms_")
                         report["kernel_tb_per_s"][api] = {"avg_us": round(avg_ns / 1e3, 2), "calls": int(row.get("Calls") or 0),
                                                           "tb_per_s": round(BYTES[api] / avg_ns / 1e3, 3)}
             kt = report["kernel_tb_per_s"]
