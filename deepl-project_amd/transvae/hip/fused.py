@@ -17,103 +17,17 @@ Math and parameter layouts are those of ops.py; reference lines are cited there 
 """
 from __future__ import annotations
 
-import os
-
 import torch
 
 from . import _lib as L
 from . import ops
-from .ops import BF16, _p, _stream, conv_dgrad, conv_forward, conv_wgrad
+from .ops import (BF16, _p, _stream, conv_dgrad, conv_forward, conv_wgrad,
+                  gn_silu_apply, gn_silu_bwd, gn_silu_fwd, rownorm_bwd, rownorm_fwd)   # (the norm launches: also read from here by tests and tools)
 
 GELU, SILU, NONE = L.ACT_GELU, L.ACT_SILU, L.ACT_NONE
-# what the forward saves for an activation: its derivative (default) or the pre-activation (TV_SAVE_DERIV=0, A/B timing)
-_SAVE_DERIV = os.environ.get("TV_SAVE_DERIV", "1") != "0"
-_WANT = "deriv" if _SAVE_DERIV else True
-
-
-def _aux_act(act_id: int) -> int:
-    return L.ACT_DERIV if _SAVE_DERIV else act_id
-
-
-# ------------------------------------------------------------------------------------------------
-# raw GroupNorm / row-norm / attention calls
-# ------------------------------------------------------------------------------------------------
-# Ablation hooks for UPPER BOUNDS on two fusions that are not built (VERDICT r03 row g; results are wrong by construction, only the
-# step time is read; bench.py refuses TV_* variables unless --allow-tuning-env and prints them into config.tuning_env):
-#   TV_ABL_SKIP_GN_STATS=1    no tv_gn_stats pass: statistics from a cached constant (mean = the pivot pixel, variance 1) -- what
-#                             GroupNorm statistics in the producing convolution's epilogue could save AT MOST (the epilogue work is free here)
-#   TV_ABL_SKIP_ROWNORM_FWD=1 no x-hat pass in front of the QKV / Conv-FFN projections (the first x-hat of a shape is reused: finite, wrong)
-#                             -- what x-hat inside the GEMM could save at most
-_ABL_SKIP_GN_STATS = os.environ.get("TV_ABL_SKIP_GN_STATS") == "1"
-_ABL_SKIP_ROWNORM_FWD = os.environ.get("TV_ABL_SKIP_ROWNORM_FWD") == "1"
-_abl_stats = {}
-
-
-def gn_silu_fwd(x, gamma, beta, groups, eps):
-    B, H, W, Cc = x.shape
-    lib = L.load()
-    if _ABL_SKIP_GN_STATS:
-        key = (B, H * W, Cc, x.device)
-        stats = _abl_stats.get(key)
-        if stats is None:
-            stats = torch.zeros((B, Cc, 2), dtype=torch.float32, device=x.device)
-            stats[..., 1] = float(H * W)
-            _abl_stats[key] = stats
-    else:
-        stats = torch.empty((B, Cc, 2), dtype=torch.float32, device=x.device)
-        part = torch.empty((lib.tv_gn_partial_count(B, H * W, Cc),), dtype=torch.float32, device=x.device)
-        L.check(lib.tv_gn_stats(_p(x), _p(stats), _p(part), B, H * W, Cc, _stream()), "tv_gn_stats")
-    mr = torch.empty((B, groups, 2), dtype=torch.float32, device=x.device)
-    y = torch.empty_like(x)
-    L.check(lib.tv_gn_silu_fwd(_p(x), _p(stats), _p(gamma), _p(beta), _p(mr), _p(y), B, H * W, Cc, groups, eps, _stream()),
-            "tv_gn_silu_fwd")
-    return y, mr
-
-
-def gn_silu_apply(x, mr, gamma, beta, groups):
-    """silu(groupnorm(x)) recomputed from saved mean / rstd (bit-identical to gn_silu_fwd's output)."""
-    B, H, W, Cc = x.shape
-    y = torch.empty_like(x)
-    L.check(L.load().tv_gn_silu_apply(_p(x), _p(mr), _p(gamma), _p(beta), _p(y), B, H * W, Cc, groups, _stream()), "tv_gn_silu_apply")
-    return y
-
-
-def gn_silu_bwd(x, dy, dres, mr, gamma, beta, groups):
-    """(dx [+ dres], dgamma, dbeta)"""
-    B, H, W, Cc = x.shape
-    lib = L.load()
-    red = torch.empty((B, Cc, 2), dtype=torch.float32, device=x.device)
-    part = torch.empty((lib.tv_gn_partial_count(B, H * W, Cc),), dtype=torch.float32, device=x.device)
-    L.check(lib.tv_gn_silu_bwd_reduce(_p(x), _p(dy), _p(mr), _p(gamma), _p(beta), _p(red), _p(part), B, H * W, Cc, groups,
-                                      _stream()), "tv_gn_silu_bwd_reduce")
-    dx = torch.empty_like(x)
-    dg = ops.zeros_f32((Cc,), x.device)
-    db = ops.zeros_f32((Cc,), x.device)
-    L.check(lib.tv_gn_silu_bwd_apply(_p(x), _p(dy), _p(dres), _p(mr), _p(red), _p(gamma), _p(beta), _p(dx), _p(dg), _p(db),
-                                     B, H * W, Cc, groups, _stream()), "tv_gn_silu_bwd_apply")
-    return dx, dg, db
-
-
-def rownorm_fwd(x, w, mode, eps_rms, eps_ln):
-    T, Cc = x.shape
-    if _ABL_SKIP_ROWNORM_FWD:       # (timing ablation: the first x-hat of this shape stands in for every later one -- finite, wrong)
-        hit = _abl_stats.get(("rownorm", T, Cc, mode, x.device))
-        if hit is not None:
-            return hit
-    y = torch.empty_like(x)
-    L.check(L.load().tv_rownorm_fwd(_p(x), _p(w), _p(y), T, Cc, mode, eps_rms, eps_ln, _stream()), "tv_rownorm_fwd")
-    if _ABL_SKIP_ROWNORM_FWD:
-        _abl_stats[("rownorm", T, Cc, mode, x.device)] = y
-    return y
-
-
-def rownorm_bwd(x, w, dy, dres, mode, eps_rms, eps_ln):
-    T, Cc = x.shape
-    dx = torch.empty_like(x)
-    dw = ops.zeros_f32((Cc,), x.device) if mode == 1 else None
-    L.check(L.load().tv_rownorm_bwd(_p(x), _p(w), _p(dy), _p(dres), _p(dx), _p(dw), T, Cc, mode, eps_rms, eps_ln, _stream()),
-            "tv_rownorm_bwd")
-    return dx, dw
+# The forward epilogue saves act'(pre-activation) for every activation the backward needs (want_pre="deriv"); the backward
+# epilogues multiply by it (aux_act=L.ACT_DERIV).
+DERIV = L.ACT_DERIV
 
 
 def _c(t):
@@ -178,24 +92,6 @@ def fold(weights, gammas, betas=None):
     return FoldFn.apply(n, *weights, *gammas, *betas)
 
 
-import os
-
-# Weight gradients do not feed the data-gradient chain, so they CAN run on a side stream (TV_WGRAD_SIDE_STREAM=1) to
-# fill the partial last wave of the dgrad launches.  Measured on MI355X (Large, bs256): 104.5 img/s with, 105.5 without
-# -- the two GEMM streams just compete for the same CUs -- so it is OFF by default.  When on: outputs are allocated on
-# the main stream (the caching allocator must see their consumer stream), the side stream waits for the producer of
-# `gz`, and the main stream joins the side stream before the Function returns.
-_SIDE = {"on": os.environ.get("TV_WGRAD_SIDE_STREAM", "0") == "1", "streams": {}}
-
-
-def _side_stream(device):
-    st = _SIDE["streams"].get(device)
-    if st is None:
-        st = torch.cuda.Stream(device=device)
-        _SIDE["streams"][device] = st
-    return st
-
-
 def _stash(ctx, *pairs):
     """pairs of (input index, tensor): remember which nn.Parameter each weight / bias input is, for in-place accumulation"""
     ctx.gparams = {i: ops.param_of(t) for i, t in pairs}
@@ -206,33 +102,16 @@ def _wg(ctx, iw, ib, geo, w, x, gz):
     need_w, need_b = ctx.needs_input_grad[iw], ctx.needs_input_grad[ib]
     if not (need_w or need_b):
         return None, None
-    if need_w and geo.mode != "shuf":
+    if need_w and geo.accumulates:      # (the mode's weight gradient has an in-place form)
         gp = getattr(ctx, "gparams", None)
         views = ops.grad_views(gp.get(iw), w, gp.get(ib), need_b) if gp else None
         if views is not None:      # micro-batch >= 2 of a step: add straight into param.grad, nothing for autograd to do
-            if geo.mode == "c3up":
-                conv_wgrad(geo, w, x, gz, need_b, out=views, accumulate=True)
-            else:
-                ops.wgrad_acc(geo.fwd_desc(0), x, gz, views[0], views[1])
+            conv_wgrad(geo, w, x, gz, need_b, out=views, accumulate=True)
             ops.acc_stats["in_place"] += 1
             return None, None
         ops.acc_stats["autograd"] += 1
-    if _SIDE["on"] and geo.mode not in ("shuf", "c3up"):
-        out = ops.conv_wgrad_alloc(geo, w, need_b, x, gz)
-        main = torch.cuda.current_stream()
-        side = _side_stream(x.device)
-        side.wait_stream(main)                      # gz (and the zero fills) are ready
-        with torch.cuda.stream(side):
-            dw, db = conv_wgrad(geo, w, x, gz, need_b, out=out)
-        ctx._side_used = True
-    else:
-        dw, db = conv_wgrad(geo, w, x, gz, need_b)
+    dw, db = conv_wgrad(geo, w, x, gz, need_b)
     return (dw if need_w else None), db
-
-
-def _join(ctx, device):
-    if getattr(ctx, "_side_used", False):
-        torch.cuda.current_stream().wait_stream(_side_stream(device))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -283,7 +162,6 @@ class ResBlockFn(torch.autograd.Function):
         dw1, dc1b = _wg(ctx, 3, 4, geo1, w1, a1, dh1)
         del a1
         dx, dg1, db1 = gn_silu_bwd(x, da1, g, mr1, g1, b1, 32)    # + skip-connection gradient, fused
-        _join(ctx, x.device)
         return dx, dg1, db1, dw1, dc1b, dg2, db2, dw2, dc2b, None, None, None
 
 
@@ -328,7 +206,6 @@ class AttnBranchFn(torch.autograd.Function):
         dxh = conv_dgrad(geo_q, wq, dqkv, xh.shape)
         dwq, dbq = _wg(ctx, 2, 3, geo_q, wq, xh, dqkv)
         dt, dw_rms = rownorm_bwd(t, w_rms, dxh, g, 1, eps_rms, eps_ln)     # + residual gradient, fused
-        _join(ctx, t.device)
         return dt, dw_rms, dwq, dbq, dwp, dbp, None, None, None, None, None, None, None
 
 
@@ -344,10 +221,10 @@ class ConvFFNBranchFn(torch.autograd.Function):
         train = any(ctx.needs_input_grad)
         b3, b_out = _c(b3), _c(b_out)
         r = rownorm_fwd(t, None, 0, eps_rms, 1e-5)
-        u, pre_u, geo_in, w_in_c = conv_forward(r, w_in, _c(b_in), None, "linear", GELU, train and _WANT)
-        c1, pre_c1, geo1, w1c = conv_forward(u, w1, _c(b1), None, "linear", GELU, train and _WANT)
+        u, pre_u, geo_in, w_in_c = conv_forward(r, w_in, _c(b_in), None, "linear", GELU, train and "deriv")
+        c1, pre_c1, geo1, w1c = conv_forward(u, w1, _c(b1), None, "linear", GELU, train and "deriv")
         mid = c1.shape[1]
-        c2, pre_c2, geo2, w2c = conv_forward(c1.view(B, H, W, mid), w2, _c(b2), None, "c3s1", GELU, train and _WANT)
+        c2, pre_c2, geo2, w2c = conv_forward(c1.view(B, H, W, mid), w2, _c(b2), None, "c3s1", GELU, train and "deriv")
         w3c, w_out_c = w3.contiguous(), w_out.contiguous()
         wc_f, wc_t, bc, wcat_f = ops.ffn_collapsed_operands(w_out_c, w3c, b3, b_out)
         # t + [u | c2] [W_out | Wc]^T + bc over the K-concatenation (one GEMM, nothing of [T, 4d + d] exists); shapes whose tile
@@ -400,23 +277,22 @@ class ConvFFNBranchFn(torch.autograd.Function):
         dw_out, db_out = _wg(ctx, 9, 10, geo_out, w_out, u, g)                          # direct part: g^T u, sum_t g
         if dwo_chain is not None and need[9]:
             dw_out = dwo_chain if dw_out is None else dw_out.add_(dwo_chain)
-        gz_c2 = ops.gemm_rows(g, wc_t, mid, aux=pre_c2.view(T, mid), aux_act=_aux_act(GELU))    # (g Wc) * gelu'(pre_c2)
+        gz_c2 = ops.gemm_rows(g, wc_t, mid, aux=pre_c2.view(T, mid), aux_act=DERIV)    # (g Wc) * gelu'(pre_c2)
         gz_c2 = gz_c2.view(B, H, W, mid)
-        gz_c1 = conv_dgrad(geo2, w2, gz_c2, (B, H, W, mid), aux=pre_c1.view(B, H, W, mid), aux_act=_aux_act(GELU))
+        gz_c1 = conv_dgrad(geo2, w2, gz_c2, (B, H, W, mid), aux=pre_c1.view(B, H, W, mid), aux_act=DERIV)
         dw2, db2 = _wg(ctx, 5, 6, geo2, w2, c1.view(B, H, W, mid), gz_c2)
         gz_c1 = gz_c1.view(T, mid)
         # d u = (g W_out + gz_c1 W1) * gelu'(pre_u) as ONE GEMM over the K-concatenation [g | gz_c1] (ops.ffn_du_operand)
         w_du = ops.ffn_du_operand(w_out, w1)
-        gz_u = ops.gemm_rows2(g, gz_c1, w_du, hid, aux=pre_u, aux_act=_aux_act(GELU)) if _SAVE_DERIV else None
+        gz_u = ops.gemm_rows2(g, gz_c1, w_du, hid, aux=pre_u, aux_act=DERIV)
         if gz_u is None:
             cat = torch.cat([g, gz_c1], dim=1)
-            gz_u = ops.gemm_rows(cat, w_du, hid, aux=pre_u, aux_act=_aux_act(GELU))
+            gz_u = ops.gemm_rows(cat, w_du, hid, aux=pre_u, aux_act=DERIV)
             del cat
         dw1, db1 = _wg(ctx, 3, 4, geo1, w1, u, gz_c1)
         dr = conv_dgrad(geo_in, w_in, gz_u, r.shape)
         dw_in, db_in = _wg(ctx, 1, 2, geo_in, w_in, r, gz_u)
         dt, _ = rownorm_bwd(t, None, dr, g, 0, eps_rms, 1e-5)                           # + residual gradient, fused
-        _join(ctx, t.device)
         if deferred:
             dw3 = db3 = None
         return (dt, dw_in, db_in, dw1, db1, dw2, db2, dw3 if need[7] else None, db3 if need[8] else None,
@@ -433,7 +309,7 @@ class DownsampleFn(torch.autograd.Function):
         dc, gdc, wdcc = None, None, None
         if wdc is not None:
             dc, _, gdc, wdcc = conv_forward(x, wdc, _c(bdc), None, "unshuf", NONE, False)
-        h, pre_h, g0, w0c = conv_forward(x, w0, _c(b0), None, "c3s1", SILU, any(ctx.needs_input_grad) and _WANT)
+        h, pre_h, g0, w0c = conv_forward(x, w0, _c(b0), None, "c3s1", SILU, any(ctx.needs_input_grad) and "deriv")
         out, _, g2, w2c = conv_forward(h, w2, _c(b2), dc, "c3s2", NONE, False)
         ctx.geo = (g0, g2, gdc)
         _stash(ctx, (1, w0), (2, b0), (3, w2), (4, b2), (5, wdc), (6, bdc))
@@ -445,7 +321,7 @@ class DownsampleFn(torch.autograd.Function):
         x, h, pre_h, w0, w2, wdc = ctx.saved_tensors
         g0, g2, gdc = ctx.geo
         g = g.contiguous()
-        gz_h = conv_dgrad(g2, w2, g, h.shape, aux=pre_h, aux_act=_aux_act(SILU))
+        gz_h = conv_dgrad(g2, w2, g, h.shape, aux=pre_h, aux_act=DERIV)
         dw2, db2 = _wg(ctx, 3, 4, g2, w2, h, g)
         dx = conv_dgrad(g0, w0, gz_h, x.shape)
         dw0, db0 = _wg(ctx, 1, 2, g0, w0, x, gz_h)
@@ -453,7 +329,6 @@ class DownsampleFn(torch.autograd.Function):
         if wdc is not None:
             dx = conv_dgrad(gdc, wdc, g, x.shape, residual=dx)                          # DC-path gradient + main path, fused
             dwdc, dbdc = _wg(ctx, 5, 6, gdc, wdc, x, g)
-        _join(ctx, x.device)
         return dx, dw0, db0, dw2, db2, dwdc, dbdc
 
 
@@ -464,7 +339,7 @@ class UpsampleFn(torch.autograd.Function):
         dc, gdc, wdcc = None, None, None
         if wdc is not None:
             dc, _, gdc, wdcc = conv_forward(x, wdc, _c(bdc), None, "shuf", NONE, False)
-        h, pre_h, g1, w1c = conv_forward(x, w1, _c(b1), None, "c3up", SILU, any(ctx.needs_input_grad) and _WANT)
+        h, pre_h, g1, w1c = conv_forward(x, w1, _c(b1), None, "c3up", SILU, any(ctx.needs_input_grad) and "deriv")
         out, _, g3, w3c = conv_forward(h, w3, _c(b3), dc, "c3s1", NONE, False)
         ctx.geo = (g1, g3, gdc)
         _stash(ctx, (1, w1), (2, b1), (3, w3), (4, b3), (5, wdc), (6, bdc))
@@ -476,7 +351,7 @@ class UpsampleFn(torch.autograd.Function):
         x, h, pre_h, w1, w3, wdc = ctx.saved_tensors
         g1, g3, gdc = ctx.geo
         g = g.contiguous()
-        gz_h = conv_dgrad(g3, w3, g, h.shape, aux=pre_h, aux_act=_aux_act(SILU))
+        gz_h = conv_dgrad(g3, w3, g, h.shape, aux=pre_h, aux_act=DERIV)
         dw3, db3 = _wg(ctx, 3, 4, g3, w3, h, g)
         dx = conv_dgrad(g1, w1, gz_h, x.shape)
         dw1, db1 = _wg(ctx, 1, 2, g1, w1, x, gz_h)
@@ -484,5 +359,4 @@ class UpsampleFn(torch.autograd.Function):
         if wdc is not None:
             dx = conv_dgrad(gdc, wdc, g, x.shape, residual=dx)
             dwdc, dbdc = _wg(ctx, 5, 6, gdc, wdc, x, g)
-        _join(ctx, x.device)
         return dx, dw1, db1, dw3, db3, dwdc, dbdc

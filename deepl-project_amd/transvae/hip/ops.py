@@ -6,13 +6,15 @@ are bf16 NHWC ([B, H, W, C] contiguous; token matrices are [T, C]); parameters s
 copies owned by the nn.Module and are repacked to bf16 per call (the repack of all 1.05 B
 parameters costs ~2 ms, three orders of magnitude below a train step).
 
-Layer "modes" of :class:`ConvFn` (geometry table in include/transvae_hip.h):
+Layer "modes" of :class:`ConvFn` (geometry table in include/transvae_hip.h; what each means to the three passes is the
+one table `_MODES` below, which every function here reads):
     linear  nn.Linear / 1x1 conv on a token matrix
     c3s1    Conv2d 3x3 stride 1 pad 1            (R/transvae/modules/blocks.py:34,37 ...)
     c3s2    Conv2d 3x3 stride 2 pad 1            (upsample.py:36)
     c3up    nearest-x2 upsample + Conv2d 3x3     (upsample.py:94-95), upsample never materialised
     unshuf  pixel_unshuffle(2) + 1x1             (upsample.py:60-61)  == 2x2 / stride-2 conv
     shuf    1x1 + pixel_shuffle(2)               (upsample.py:121-123) == GEMM with shuffled store
+    c4s2 / c4s1   Conv2d 4x4 pad 1 at stride 2 / 1  (the PatchGAN discriminator of transvae/models/discriminator.py)
     c3v1 / c3v2 / c5s1 / c1   Conv2d 3x3 unpadded at stride 1 / 2, 5x5 pad 2, 1x1 on NHWC: forward only (the frozen FID
                               Inception-v3 of transvae/metrics_fid.py; conv_dgrad raises on them)
 """
@@ -20,8 +22,9 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import dataclasses
 import functools
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -169,9 +172,8 @@ def pack_weight(w: torch.Tensor, want_fwd: bool, want_t: bool, flip: bool):
     """w: fp32 [O, T, I] contiguous -> (bf16 [O,T,I] | None, bf16 [I,T,O] | None)."""
     O, T, I = w.shape
     _require(w.dtype == torch.float32 and w.is_contiguous(), "pack_weight needs a contiguous fp32 [O, T, I] tensor")
-    base = w._base if w._base is not None else w
-    is_param = isinstance(base, torch.nn.Parameter)
-    if is_param:
+    base = param_of(w)
+    if base is not None:
         ent = _operands_of(base)
         if ent is not None:          # operands kept current by the optimizer: no kernel here
             off = (w.data_ptr() - base.data_ptr()) // 4
@@ -186,30 +188,30 @@ def pack_weight(w: torch.Tensor, want_fwd: bool, want_t: bool, flip: bool):
                         L.check(L.load().tv_pack_weight(_p(w), None, _p(dt), O, T, I, int(flip), _stream()), "tv_pack_weight")
                         ent.forms[fk] = dt
                 return d, dt
-    key = None
-    if _pack_cache is not None and is_param:
-        key = (id(base), base._version, w.data_ptr(), O, T, I, want_fwd, want_t, flip)
-        hit = _pack_cache.get(key)
-        if hit is not None:
-            return hit
-    d = torch.empty((O, T, I), dtype=BF16, device=w.device) if want_fwd else None
-    dt = torch.empty((I, T, O), dtype=BF16, device=w.device) if want_t else None
-    lib = L.load()
-    L.check(lib.tv_pack_weight(_p(w), _p(d), _p(dt), O, T, I, int(flip), _stream()), "tv_pack_weight")
-    if key is not None:
-        _pack_cache[key] = (d, dt)
-    return d, dt
+
+    def build():
+        d = torch.empty((O, T, I), dtype=BF16, device=w.device) if want_fwd else None
+        dt = torch.empty((I, T, O), dtype=BF16, device=w.device) if want_t else None
+        L.check(L.load().tv_pack_weight(_p(w), _p(d), _p(dt), O, T, I, int(flip), _stream()), "tv_pack_weight")
+        return d, dt
+    return _step_cached((w,), ("pack", O, T, I, want_fwd, want_t, flip), build)
 
 
-def _derived_weight(w: torch.Tensor, kind: str, build):
-    """Operands DERIVED from a parameter by a chain of small torch ops (polyphase / parity forms): same cache, same key
-    rule as pack_weight -- they cost 50-100 launch-bound kernels each, once per optimizer step instead of per micro-batch."""
+def _step_cached(views, kind, build):
+    """build(), once per optimizer step: THE rule for every operand derived from parameters (bf16 repacks, the polyphase /
+    parity forms at 50-100 launch-bound kernels each, the Conv-FFN composites).  Inside a packed_weight_cache() block the
+    result is kept under `kind`, the id and version counter of the parameter behind each view and the view's address, so an
+    in-place update of a parameter invalidates it; a view of anything else (tensors computed per forward), or no open
+    block, builds afresh.  `views` may hold None (an absent bias)."""
     if _pack_cache is None:
         return build()
-    base = w._base if w._base is not None else w
-    if not isinstance(base, torch.nn.Parameter):
-        return build()
-    key = (id(base), base._version, w.data_ptr(), tuple(w.shape), kind)
+    key = [kind]
+    for v in views:
+        base = param_of(v)
+        if base is None and v is not None:
+            return build()
+        key.append(None if v is None else (id(base), base._version, v.data_ptr()))
+    key = tuple(key)
     hit = _pack_cache.get(key)
     if hit is None:
         hit = _pack_cache[key] = build()
@@ -254,41 +256,48 @@ def _row_ptr(t, batch: int, row: int):
     """device pointer of row `row` of a tensor with `batch` leading rows (None stays None)"""
     if t is None:
         return None
-    return C.c_void_p(t.data_ptr() + row * (t.numel() // batch) * t.element_size())
+    return C.c_void_p(t.data_ptr() + (row * (t.numel() // batch) * t.element_size() if row else 0))
 
 
-def _desc_rows(desc: L.ConvDesc, rows: int) -> L.ConvDesc:
+def _desc_like(desc: L.ConvDesc, **fields) -> L.ConvDesc:
+    """a copy of `desc` with some fields replaced"""
     d = L.ConvDesc()
     C.memmove(C.byref(d), C.byref(desc), C.sizeof(L.ConvDesc))
-    d.batch = rows
+    for k, v in fields.items():
+        setattr(d, k, int(v))
     return d
 
 
-def igemm(desc: L.ConvDesc, x, w, bias, residual, pre, out):
+def _launch(entry: str, desc: L.ConvDesc, args, align: int = 1, later: Optional[str] = None):
+    """lib.<entry>(&desc, *args, stream) -- in one launch, or one per batch chunk where an activation passes the launch limit.
+    Tensors in `args` are the activations: desc.batch leading rows each, sliced per chunk (None stays None); everything else
+    (packed operands as _p(...), integers) is passed as it is.  align: chunks are multiples of so many rows;  later: the
+    entry point of the chunks after the first."""
     lib = L.load()
-    ch = _batch_chunks(desc.batch, (x, residual, pre, out))
-    if ch is None:
-        L.check(lib.tv_igemm_nt(C.byref(desc), _p(x), _p(w), _p(bias), _p(residual), _p(pre), _p(out), _stream()), "tv_igemm_nt")
-        return
     B = desc.batch
-    for s, c in ch:
-        L.check(lib.tv_igemm_nt(C.byref(_desc_rows(desc, c)), _row_ptr(x, B, s), _p(w), _p(bias), _row_ptr(residual, B, s),
-                                _row_ptr(pre, B, s), _row_ptr(out, B, s), _stream()), "tv_igemm_nt")
+    ch = _batch_chunks(B, [a for a in args if isinstance(a, torch.Tensor)], align)
+    for i, (s, c) in enumerate(ch or ((0, B),)):
+        d = desc if ch is None else _desc_like(desc, batch=c)
+        fn = getattr(lib, later if (i and later) else entry)
+        L.check(fn(C.byref(d), *[_row_ptr(a, B, s) if isinstance(a, torch.Tensor) else a for a in args], _stream()), entry)
+
+
+def igemm(desc: L.ConvDesc, x, w, bias, residual, pre, out):
+    _launch("tv_igemm_nt", desc, (x, _p(w), _p(bias), residual, pre, out))
+
+
+def _igemm_bwd(desc, gz, wt, residual, aux, aux_act, dx):
+    """dx = conv(gz, wt) [+ residual] [* act'(aux)]"""
+    if aux is None:
+        igemm(desc, gz, wt, None, residual, None, dx)
+    else:
+        _launch("tv_igemm_nt_actgrad", desc, (gz, _p(wt), residual, aux, aux_act, dx))
 
 
 def wgrad(desc: L.ConvDesc, x, gy, dw, dbias, _acc: bool = False):
     """dw (and dbias) of one layer.  Chunked launches: the first chunk follows the kernel's own overwrite / accumulate
     plan for ITS geometry (callers size-check with wgrad_plan_desc), later chunks add."""
-    lib = L.load()
-    ch = _batch_chunks(desc.batch, (x, gy))
-    fn_first = lib.tv_wgrad_tn_acc if _acc else lib.tv_wgrad_tn
-    if ch is None:
-        L.check(fn_first(C.byref(desc), _p(x), _p(gy), _p(dw), _p(dbias), _stream()), "tv_wgrad_tn")
-        return
-    B = desc.batch
-    for i, (s, c) in enumerate(ch):
-        fn = fn_first if i == 0 else lib.tv_wgrad_tn_acc
-        L.check(fn(C.byref(_desc_rows(desc, c)), _row_ptr(x, B, s), _row_ptr(gy, B, s), _p(dw), _p(dbias), _stream()), "tv_wgrad_tn")
+    _launch("tv_wgrad_tn_acc" if _acc else "tv_wgrad_tn", desc, (x, gy, _p(dw), _p(dbias)), later="tv_wgrad_tn_acc")
 
 
 def wgrad_acc(desc: L.ConvDesc, x, gy, dw, dbias):
@@ -299,7 +308,7 @@ def wgrad_acc(desc: L.ConvDesc, x, gy, dw, dbias):
 def wgrad_plan_desc(desc: L.ConvDesc, x, gy) -> L.ConvDesc:
     """The descriptor of the FIRST launch of wgrad(desc, x, gy, ...): what tv_wgrad_tn_overwrites must be asked about."""
     ch = _batch_chunks(desc.batch, (x, gy))
-    return desc if ch is None else _desc_rows(desc, ch[0][1])
+    return desc if ch is None else _desc_like(desc, batch=ch[0][1])
 
 
 # In-place gradient accumulation across the micro-batches of one optimizer step (transvae.parallel.train_step switches it on
@@ -396,147 +405,6 @@ def _ones(n: int, device) -> torch.Tensor:
 # ---------------------------------------------------------------------------------------------
 # convolution / linear
 # ---------------------------------------------------------------------------------------------
-class _Geo:
-    """Shapes of one layer instance, derived from mode + tensor shapes."""
-
-    def __init__(self, mode: str, x: torch.Tensor, w: torch.Tensor):
-        self.mode = mode
-        if mode == "linear":
-            _require(x.dim() == 2 and w.dim() == 2, "operand check failed: x.dim() == 2 and w.dim() == 2")
-            self.B, self.H, self.W, self.Cin = x.shape[0], 1, 1, x.shape[1]
-            self.Cout, self.KH, self.KW = w.shape[0], 1, 1
-            self.Ho, self.Wo = 1, 1
-            self.out_shape = (self.B, self.Cout)
-        else:
-            _require(x.dim() == 4 and w.dim() == 4, "operand check failed: " + repr((mode, x.shape, w.shape)))
-            self.B, self.H, self.W, self.Cin = x.shape
-            self.Cout, self.KH, self.KW = w.shape[0], w.shape[1], w.shape[2]
-            if mode == "c3s1":
-                self.Ho, self.Wo = self.H, self.W
-            elif mode in ("c3s2", "unshuf"):
-                _require(self.H % 2 == 0 and self.W % 2 == 0, "operand check failed: self.H % 2 == 0 and self.W % 2 == 0")
-                self.Ho, self.Wo = self.H // 2, self.W // 2
-            elif mode == "c3up":
-                self.Ho, self.Wo = 2 * self.H, 2 * self.W
-            elif mode == "c4s2":   # 4x4 / stride 2 / pad 1 (PatchGAN discriminator)
-                _require(self.H % 2 == 0 and self.W % 2 == 0, "operand check failed: self.H % 2 == 0 and self.W % 2 == 0")
-                self.Ho, self.Wo = self.H // 2, self.W // 2
-            elif mode == "c4s1":   # 4x4 / stride 1 / pad 1: the grid shrinks by one (odd grids occur)
-                _require(self.H >= 2 and self.W >= 2, "operand check failed: self.H >= 2 and self.W >= 2")
-                self.Ho, self.Wo = self.H - 1, self.W - 1
-            elif mode == "c3v1":   # 3x3 / stride 1 / no padding (the Inception stem): forward only, like the three modes below
-                _require(self.H >= 3 and self.W >= 3, "operand check failed: self.H >= 3 and self.W >= 3")
-                self.Ho, self.Wo = self.H - 2, self.W - 2
-            elif mode == "c3v2":   # 3x3 / stride 2 / no padding, floor
-                _require(self.H >= 3 and self.W >= 3, "operand check failed: self.H >= 3 and self.W >= 3")
-                self.Ho, self.Wo = (self.H - 3) // 2 + 1, (self.W - 3) // 2 + 1
-            elif mode in ("c5s1", "c1"):   # 5x5 / stride 1 / pad 2; 1x1 on an NHWC tensor
-                self.Ho, self.Wo = self.H, self.W
-            elif mode == "shuf":
-                _require(self.KH == 1 and self.KW == 1 and self.Cout % 4 == 0, "operand check failed: self.KH == 1 and self.KW == 1 and self.Cout % 4 == 0")
-                self.Ho, self.Wo = self.H, self.W          # GEMM grid; stored to [B,2H,2W,Cout/4]
-            else:
-                raise ValueError(f"unknown conv mode {mode}")
-            if mode == "shuf":
-                self.out_shape = (self.B, 2 * self.H, 2 * self.W, self.Cout // 4)
-            else:
-                self.out_shape = (self.B, self.Ho, self.Wo, self.Cout)
-        _require(w.shape[-1] == self.Cin, "operand check failed: " + repr((mode, tuple(x.shape), tuple(w.shape))))
-        exp_k = {"linear": (1, 1), "c3s1": (3, 3), "c3s2": (3, 3), "c3up": (3, 3), "unshuf": (2, 2), "shuf": (1, 1), "c4s2": (4, 4),
-                 "c4s1": (4, 4), "c3v1": (3, 3), "c3v2": (3, 3), "c5s1": (5, 5), "c1": (1, 1)}[mode]
-        _require((self.KH, self.KW) == exp_k, "operand check failed: " + repr((mode, tuple(w.shape))))
-
-    def fwd_desc(self, act: int) -> L.ConvDesc:
-        m = self.mode
-        common = dict(batch=self.B, h_in=self.H, w_in=self.W, c_in=self.Cin, ldx=self.Cin,
-                      h_out=self.Ho, w_out=self.Wo, c_out=self.Cout, ldo=self.Cout,
-                      kh=self.KH, kw=self.KW, act=act)
-        if m == "linear":
-            return _desc(**common)
-        if m == "c3s1":
-            return _desc(**common, stride=1, pad=1)
-        if m == "c3s2":
-            return _desc(**common, stride=2, pad=1)
-        if m == "c3up":
-            return _desc(**common, stride=1, pad=1, up_shift=1)
-        if m == "unshuf":
-            return _desc(**common, stride=2, pad=0)
-        if m == "c4s2":
-            return _desc(**common, stride=2, pad=1)
-        if m == "c4s1":
-            return _desc(**common, stride=1, pad=1)
-        if m == "c3v1":
-            return _desc(**common, stride=1, pad=0)
-        if m == "c3v2":
-            return _desc(**common, stride=2, pad=0)
-        if m == "c5s1":
-            return _desc(**common, stride=1, pad=2)
-        if m == "c1":
-            return _desc(**common)
-        if m == "shuf":
-            common["ldo"] = self.Cout // 4
-            return _desc(**common, store_shuffle=1)
-        raise ValueError(m)
-
-
-# ---- the three passes of one layer as plain functions (shared by ConvFn and the fused block Functions) ----
-def conv_forward(x, w, bias, residual, mode: str, act_id: int, want_pre, rope=None):
-    """Returns (out, pre_activation | None, geometry, contiguous fp32 weight).
-    rope = (table [N, 4, 32] fp32, tokens per image N, columns to rotate): 'linear' only -- the QKV projection with RoPE in
-    its epilogue (tv_igemm_nt_rope).
-    want_pre = "deriv": the second tensor is act'(pre-activation) instead (pass it to conv_dgrad with
-    aux_act = L.ACT_DERIV); falsy: nothing is saved."""
-    _need_gpu(x, w)
-    _require(x.dtype == BF16 and x.is_contiguous(), "activations must be contiguous bf16 NHWC")
-    _require(w.dtype == torch.float32, f"weights must be fp32 master copies, got {w.dtype} (parameter algebra under autocast?)")
-    _require(x.device == w.device and x.device.index == torch.cuda.current_device(),
-             f"tensors on {x.device} / {w.device} but the current device is cuda:{torch.cuda.current_device()}")
-    w = w.contiguous()
-    g = _Geo(mode, x, w)
-    out = torch.empty(g.out_shape, dtype=BF16, device=x.device)
-    pre = torch.empty_like(out) if (want_pre and act_id != L.ACT_NONE) else None
-    if pre is not None and want_pre == "deriv":
-        act_id |= L.ACT_SAVE_DERIV
-    if residual is not None:
-        _require(residual.shape == out.shape and residual.dtype == BF16 and residual.is_contiguous(),
-                 "residual must be contiguous bf16 of the output's shape")
-    if bias is not None:
-        _require(bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == g.Cout,
-                 f"bias must be contiguous fp32 [{g.Cout}], got {bias.dtype} {tuple(bias.shape)}")
-    if mode == "c3up":   # polyphase: one 2x2-footprint GEMM on the (H+1) x (W+1) cell grid, four phases as column quadrants
-        wb = _derived_weight(w, "up_fwd", lambda: _up_fwd_weight(w, g.Cout, g.Cin))
-        d = _desc(batch=g.B, h_in=g.H, w_in=g.W, c_in=g.Cin, ldx=g.Cin, h_out=g.H + 1, w_out=g.W + 1, c_out=4 * g.Cout,
-                  ldo=g.Cout, kh=2, kw=2, stride=1, pad=1, act=act_id, store_shuffle=2)
-        igemm(d, x, wb, bias.repeat(4) if bias is not None else None, residual, pre, out)
-        return out, pre, g, w
-    wb, _ = pack_weight(w.view(g.Cout, g.KH * g.KW, g.Cin), True, False, False)
-    if rope is not None:
-        tab, tokens, cols = rope
-        _require(mode == "linear" and residual is None and pre is None and act_id == L.ACT_NONE, "rope epilogue: plain projection only")
-        _require(tab.dtype == torch.float32 and tab.is_contiguous() and tuple(tab.shape) == (tokens, 4, 32) and g.B % tokens == 0,
-                 "rope table must be contiguous fp32 [tokens, 4, 32] and the rows whole images")
-        d = g.fwd_desc(act_id)
-        ch = _batch_chunks(d.batch, (x, out), align=int(tokens)) or [(0, d.batch)]
-        for s0, c0 in ch:
-            L.check(L.load().tv_igemm_nt_rope(C.byref(_desc_rows(d, c0)), _row_ptr(x, d.batch, s0), _p(wb), _p(bias), _row_ptr(out, d.batch, s0),
-                                              _p(tab), int(tokens), int(cols), _stream()), "tv_igemm_nt_rope")
-        return out, pre, g, w
-    igemm(g.fwd_desc(act_id), x, wb, bias, residual, pre, out)
-    return out, pre, g, w
-
-
-def _igemm_bwd(desc, gz, wt, residual, aux, aux_act, dx):
-    """dx = conv(gz, wt) [+ residual] [* act'(aux)]"""
-    if aux is None:
-        igemm(desc, gz, wt, None, residual, None, dx)
-    else:
-        lib = L.load()
-        B = desc.batch
-        for s, c in (_batch_chunks(B, (gz, residual, aux, dx)) or [(0, B)]):
-            L.check(lib.tv_igemm_nt_actgrad(C.byref(_desc_rows(desc, c)), _row_ptr(gz, B, s), _p(wt), _row_ptr(residual, B, s),
-                                            _row_ptr(aux, B, s), aux_act, _row_ptr(dx, B, s), _stream()), "tv_igemm_nt_actgrad")
-
-
 # nearest-x2 upsample followed by a 3x3 / pad-1 convolution, in polyphase form.  Output row Y = 2y' - py of the [2H]
 # grid reads the input rows y'-1, y' of the [H] grid (cell y' of the (H+1)-cell grid of neighbouring row pairs), because
 # upsampled rows 2r, 2r+1 are both input row r:
@@ -579,10 +447,220 @@ def _up_fold_wgrad(d16: torch.Tensor, Cout: int, Cin: int, out: Optional[torch.T
 
 
 def _s2_parity_weight(w: torch.Tensor, Cout: int, Cin: int) -> torch.Tensor:
-    """Data-gradient operand of a 3x3 / stride-2 / pad-1 convolution, by output parity (see conv_dgrad):
+    """Data-gradient operand of a 3x3 / stride-2 / pad-1 convolution, by output parity (see _MODES):
     bf16 [4*Cin, 2, 2, Cout];  row (2*py+px)*Cin + ci, tap (ty, tx) holds w[:, ky, kx, ci] with ky = 1 for py = 0 and
     ky = 2, 0 for ty = 0, 1 when py = 1 (kx likewise); taps outside the class's footprint stay zero."""
     return _derive(w.view(Cout, 3, 3, Cin), L.DERIVE_S2_PARITY, Cout, Cin, torch.empty((4 * Cin, 2, 2, Cout), dtype=BF16, device=w.device))
+
+
+# data-gradient form of the 4x4 / stride-2 convolutions ('c4s2'): "polyphase" (2x2 footprint, phase-shuffled store) or "dilated"
+# (4x4 taps over the zero-dilated gradient); tools/gan_bench.py times both
+C4S2_DGRAD_FORM = "polyphase"
+_C4S2_KY = ((3, 1), (2, 0))    # [phase][tap] -> ky
+
+
+def _c4s2_poly_weight(w: torch.Tensor, Cout: int, Cin: int) -> torch.Tensor:
+    """w fp32 [Cout, 4, 4, Cin] -> bf16 [4*Cin, 2, 2, Cout]: row (2*py+px)*Cin + ci, tap (ty, tx) = w[co, ky(py,ty), kx(px,tx), ci]."""
+    wt = w.permute(3, 1, 2, 0)                                   # [Cin, ky, kx, Cout]
+    out = torch.empty((4, Cin, 2, 2, Cout), dtype=BF16, device=w.device)
+    for py in range(2):
+        for px in range(2):
+            sel = wt[:, list(_C4S2_KY[py])][:, :, list(_C4S2_KY[px])]
+            out[2 * py + px] = sel.to(BF16)
+    return out.view(4 * Cin, 2, 2, Cout)
+
+
+# ---------------------------------------------------------------------------------------------
+# the mode table: everything a mode means, in one place
+# ---------------------------------------------------------------------------------------------
+# An entry gives the taps and the forward convolution (stride, pad, up_shift, store_shuffle); the output grid follows from
+# them by the usual rule  out = ((in << up_shift) + 2 pad - taps) // stride + 1  and `need` is what the input grid must
+# satisfy (even, or a minimum size).  _Geo, conv_forward, conv_dgrad, conv_wgrad / conv_wgrad_alloc and fused._wg read the table;
+# a new mode is one entry here.
+class _Plan(NamedTuple):
+    """One GEMM launch: how its bf16 operand is made from the fp32 weight, and the descriptor fields that differ from the
+    default it is laid over -- for `forward`, _Geo.fwd_desc; for `dgrad`, the swapped descriptor of _Geo.dgrad_desc."""
+    operand: Callable      # (g, w) -> bf16 operand
+    fields: Callable       # g -> {descriptor field: value}
+
+
+def _packed_t(flip: bool):
+    """[Cin][taps][Cout]: the packed transpose, taps reversed where the adjoint correlates with the flipped kernel"""
+    return lambda g, w: pack_weight(w.view(g.Cout, g.KH * g.KW, g.Cin), False, True, flip)[1]
+
+
+def _flat_t(g, w):
+    """GEMM rows n = (dy, dx, c): the transpose of the flattened [Cout, taps * Cin] matrix"""
+    return pack_weight(w.view(g.Cout, 1, g.KH * g.KW * g.Cin), False, True, False)[1]
+
+
+def _derived(kind: str, build):
+    """an operand derived from the parameter by `build` (polyphase / parity forms), once per optimizer step"""
+    return lambda g, w: _step_cached((w,), (kind, tuple(w.shape)), lambda: build(w, g.Cout, g.Cin))
+
+
+def _min_grid(n: int):
+    return (lambda g: g.H >= n and g.W >= n, f"self.H >= {n} and self.W >= {n}")
+
+
+_EVEN = (lambda g: g.H % 2 == 0 and g.W % 2 == 0, "self.H % 2 == 0 and self.W % 2 == 0")
+_QUADS = (lambda g: g.KH == 1 and g.KW == 1 and g.Cout % 4 == 0, "self.KH == 1 and self.KW == 1 and self.Cout % 4 == 0")
+
+
+@dataclasses.dataclass(frozen=True)
+class _Mode:
+    taps: tuple                         # (KH, KW)
+    stride: int = 1
+    pad: int = 0
+    up_shift: int = 0                   # 1: the input is read through a nearest-x2 upsample
+    store_shuffle: int = 0              # 1: the Cout columns are stored as 2 x 2 pixels of Cout / 4 channels
+    tokens: bool = False                # operands are token matrices [T, C], not NHWC
+    need: Optional[tuple] = None        # (predicate of the geometry, its text in the error)
+    forward: Optional[_Plan] = None     # the launch the forward really makes, where that is not fwd_desc + the packed weight
+    dgrad: object = None                # _Plan | {C4S2_DGRAD_FORM: _Plan} | None = forward only (conv_dgrad raises)
+    wgrad: str = "direct"               # "direct": tv_wgrad_tn on fwd_desc, accumulates in place through tv_wgrad_tn_acc
+    #                                     "fold": the adjoint problem (dgrad's descriptor, operands exchanged), then folded
+    #                                             onto the 3x3 taps; accumulates in place through the fold
+    #                                     "transposed": the adjoint problem, its result transposed; never in place
+
+
+_MODES = {
+    "linear": _Mode((1, 1), tokens=True, dgrad=_Plan(_packed_t(False), lambda g: {})),
+    "c3s1": _Mode((3, 3), pad=1, dgrad=_Plan(_packed_t(True), lambda g: dict(pad=1))),
+    # c3s2 dgrad by output parity: dx[2y+py, 2x+px] only sees the taps with ky = 1 (py = 0) or ky in {2, 0} at gz rows y, y+1
+    # (py = 1), likewise in x.  One GEMM over the low-resolution grid with a 2x2 footprint and 4*Cin columns -- class (py, px)
+    # in column quadrant 2*py+px, its unused taps zero -- stored pixel-shuffled: 16 tap-GEMMs instead of the 36 of a
+    # zero-dilated 3x3 on the full-resolution grid (9 are the algorithmic minimum).
+    "c3s2": _Mode((3, 3), stride=2, pad=1, need=_EVEN,
+                  dgrad=_Plan(_derived("s2_parity", _s2_parity_weight),
+                              lambda g: dict(h_out=g.Ho, w_out=g.Wo, c_out=4 * g.Cin, kh=2, kw=2, store_shuffle=1))),
+    # c3up forward in polyphase form: one 2x2-footprint GEMM on the (H+1) x (W+1) cell grid, the four phases as column
+    # quadrants; its adjoint is a 4x4 / stride-2 / pad-1 convolution of the high-resolution gradient, and the weight gradient
+    # is that of the adjoint (gathered operand: the gradient; the other: the layer input) folded back onto the 3x3 taps.
+    "c3up": _Mode((3, 3), pad=1, up_shift=1, wgrad="fold",
+                  forward=_Plan(_derived("up_fwd", _up_fwd_weight),
+                                lambda g: dict(h_out=g.H + 1, w_out=g.W + 1, c_out=4 * g.Cout, kh=2, kw=2, up_shift=0, store_shuffle=2)),
+                  dgrad=_Plan(_derived("up_dgrad", _up_dgrad_weight), lambda g: dict(kh=4, kw=4, stride=2, pad=1))),
+    # unshuf dgrad: dx[b,2oy+dy,2ox+dx,c] = sum_co gz[b,oy,ox,co] W[co,dy,dx,c] -> GEMM with shuffled store
+    "unshuf": _Mode((2, 2), stride=2, need=_EVEN,
+                    dgrad=_Plan(_flat_t, lambda g: dict(h_out=g.Ho, w_out=g.Wo, c_out=4 * g.Cin, kh=1, kw=1, store_shuffle=1))),
+    # shuf dgrad: dx[p,ci] = sum_{q,c} gz_hi[pix(p,q),c] W[(q,c),ci] -> 2x2 / stride-2 gather conv over the high-resolution
+    # gradient; the weight gradient is the same problem with the gradient as the gathered operand
+    "shuf": _Mode((1, 1), store_shuffle=1, need=_QUADS, wgrad="transposed",
+                  dgrad=_Plan(_packed_t(False), lambda g: dict(h_in=2 * g.H, w_in=2 * g.W, c_in=g.Cout // 4, ldx=g.Cout // 4,
+                                                               kh=2, kw=2, stride=2))),
+    # c4s2 (PatchGAN discriminator) dgrad, selected by C4S2_DGRAD_FORM:
+    #   polyphase  the adjoint of a 4x4 / stride-2 / pad-1 convolution is the polyphase upsampling convolution of 'c3up': dx row
+    #              Y = 2y - py only sees ky of one parity, at gz rows y-1 (tap 0) and y (tap 1) of cell y on the (Ho+1)-cell grid:
+    #                  py = 0: tap 0 <- ky 3, tap 1 <- ky 1        py = 1: tap 0 <- ky 2, tap 1 <- ky 0        (the same along x)
+    #              4 tap-GEMMs per output pixel instead of the 16 (12 of them on zeros) of the zero-dilated form
+    #   dilated    virtual row uy = iy + t - 2 of the zero-dilated gradient, valid where even, gz row uy / 2
+    "c4s2": _Mode((4, 4), stride=2, pad=1, need=_EVEN,
+                  dgrad={"polyphase": _Plan(_derived("c4s2_poly", _c4s2_poly_weight),
+                                            lambda g: dict(h_out=g.Ho + 1, w_out=g.Wo + 1, c_out=4 * g.Cin, kh=2, kw=2, pad=1, store_shuffle=2)),
+                         "dilated": _Plan(_packed_t(True), lambda g: dict(pad=2, up_shift=1, dil_mask=1))}),
+    # c4s1: the grid shrinks by one (odd grids occur); dx[iy] = sum_ky gz[iy + 1 - ky] w[ky]: taps reversed (t = 3 - ky), gz row
+    # iy + t - 2, i.e. pad 2
+    "c4s1": _Mode((4, 4), pad=1, need=_min_grid(2), dgrad=_Plan(_packed_t(True), lambda g: dict(pad=2))),
+    # the frozen Inception-v3 of the FID: 3x3 unpadded at stride 1 / 2 (floor), 5x5 pad 2, 1x1 on an NHWC tensor -- forward only
+    "c3v1": _Mode((3, 3), need=_min_grid(3)),
+    "c3v2": _Mode((3, 3), stride=2, need=_min_grid(3)),
+    "c5s1": _Mode((5, 5), pad=2),
+    "c1": _Mode((1, 1)),
+}
+
+
+class _Geo:
+    """Shapes of one layer instance, derived from mode + tensor shapes; descriptors and plans come from _MODES."""
+
+    def __init__(self, mode: str, x: torch.Tensor, w: torch.Tensor):
+        md = _MODES.get(mode)
+        if md is None:
+            raise ValueError(f"unknown conv mode {mode}")
+        self.mode, self.md = mode, md
+        if md.tokens:
+            _require(x.dim() == 2 and w.dim() == 2, "operand check failed: x.dim() == 2 and w.dim() == 2")
+            self.B, self.H, self.W, self.Cin = x.shape[0], 1, 1, x.shape[1]
+            self.Cout, self.KH, self.KW = w.shape[0], 1, 1
+        else:
+            _require(x.dim() == 4 and w.dim() == 4, "operand check failed: " + repr((mode, x.shape, w.shape)))
+            self.B, self.H, self.W, self.Cin = x.shape
+            self.Cout, self.KH, self.KW = w.shape[0], w.shape[1], w.shape[2]
+        if md.need is not None:
+            _require(md.need[0](self), "operand check failed: " + md.need[1])
+        self.Ho, self.Wo = (((n << md.up_shift) + 2 * md.pad - k) // md.stride + 1 for n, k in zip((self.H, self.W), md.taps))
+        if md.tokens:
+            self.out_shape = (self.B, self.Cout)
+        elif md.store_shuffle:
+            self.out_shape = (self.B, 2 * self.H, 2 * self.W, self.Cout // 4)
+        else:
+            self.out_shape = (self.B, self.Ho, self.Wo, self.Cout)
+        _require(w.shape[-1] == self.Cin, "operand check failed: " + repr((mode, tuple(x.shape), tuple(w.shape))))
+        _require((self.KH, self.KW) == md.taps, "operand check failed: " + repr((mode, tuple(w.shape))))
+        self.accumulates = md.wgrad != "transposed"     # conv_wgrad(..., accumulate=True) can add into param.grad
+
+    def fwd_desc(self, act: int) -> L.ConvDesc:
+        md = self.md
+        return _desc(batch=self.B, h_in=self.H, w_in=self.W, c_in=self.Cin, ldx=self.Cin,
+                     h_out=self.Ho, w_out=self.Wo, c_out=self.Cout, ldo=self.out_shape[-1], kh=self.KH, kw=self.KW,
+                     stride=md.stride, pad=md.pad, up_shift=md.up_shift, act=act, store_shuffle=md.store_shuffle)
+
+    def dgrad_plan(self) -> _Plan:
+        plan = self.md.dgrad
+        if isinstance(plan, dict):
+            plan = plan[C4S2_DGRAD_FORM]
+        if plan is None:
+            raise ValueError(self.mode)
+        return plan
+
+    def dgrad_desc(self) -> L.ConvDesc:
+        """The swapped problem -- the gradient in, channels and grids of the forward exchanged, the mode's taps at stride 1
+        without padding -- with the plan's fields laid over it."""
+        return _desc(**{**dict(batch=self.B, h_in=self.Ho, w_in=self.Wo, c_in=self.Cout, ldx=self.Cout,
+                               h_out=self.H, w_out=self.W, c_out=self.Cin, ldo=self.Cin, kh=self.KH, kw=self.KW),
+                        **self.dgrad_plan().fields(self)})
+
+
+# ---- the three passes of one layer as plain functions (shared by ConvFn and the fused block Functions) ----
+def conv_forward(x, w, bias, residual, mode: str, act_id: int, want_pre, rope=None):
+    """Returns (out, pre_activation | None, geometry, contiguous fp32 weight).
+    rope = (table [N, 4, 32] fp32, tokens per image N, columns to rotate): 'linear' only -- the QKV projection with RoPE in
+    its epilogue (tv_igemm_nt_rope).
+    want_pre = "deriv": the second tensor is act'(pre-activation) instead (pass it to conv_dgrad with
+    aux_act = L.ACT_DERIV); falsy: nothing is saved."""
+    _need_gpu(x, w)
+    _require(x.dtype == BF16 and x.is_contiguous(), "activations must be contiguous bf16 NHWC")
+    _require(w.dtype == torch.float32, f"weights must be fp32 master copies, got {w.dtype} (parameter algebra under autocast?)")
+    _require(x.device == w.device and x.device.index == torch.cuda.current_device(),
+             f"tensors on {x.device} / {w.device} but the current device is cuda:{torch.cuda.current_device()}")
+    w = w.contiguous()
+    g = _Geo(mode, x, w)
+    out = torch.empty(g.out_shape, dtype=BF16, device=x.device)
+    pre = torch.empty_like(out) if (want_pre and act_id != L.ACT_NONE) else None
+    if pre is not None and want_pre == "deriv":
+        act_id |= L.ACT_SAVE_DERIV
+    if residual is not None:
+        _require(residual.shape == out.shape and residual.dtype == BF16 and residual.is_contiguous(),
+                 "residual must be contiguous bf16 of the output's shape")
+    if bias is not None:
+        _require(bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == g.Cout,
+                 f"bias must be contiguous fp32 [{g.Cout}], got {bias.dtype} {tuple(bias.shape)}")
+    d = g.fwd_desc(act_id)
+    if g.md.forward is None:
+        wb, _ = pack_weight(w.view(g.Cout, g.KH * g.KW, g.Cin), True, False, False)
+    else:                   # (polyphase: every column quadrant of the GEMM is a phase of the same layer, so of the same bias)
+        wb = g.md.forward.operand(g, w)
+        d = _desc_like(d, **g.md.forward.fields(g))
+        bias = bias.repeat(d.c_out // g.Cout) if bias is not None else None
+    if rope is not None:
+        tab, tokens, cols = rope
+        _require(g.md.tokens and residual is None and pre is None and act_id == L.ACT_NONE, "rope epilogue: plain projection only")
+        _require(tab.dtype == torch.float32 and tab.is_contiguous() and tuple(tab.shape) == (tokens, 4, 32) and g.B % tokens == 0,
+                 "rope table must be contiguous fp32 [tokens, 4, 32] and the rows whole images")
+        _launch("tv_igemm_nt_rope", d, (x, _p(wb), _p(bias), out, _p(tab), int(tokens), int(cols)), align=int(tokens))
+    else:
+        igemm(d, x, wb, bias, residual, pre, out)
+    return out, pre, g, w
 
 
 # ---- Conv-FFN tail in collapsed form ---------------------------------------------------------------------------------------
@@ -651,17 +729,7 @@ def ffn_collapsed_operands(w_out: torch.Tensor, w3: torch.Tensor, b3, b_out):
         else:
             bc = b_out
         return wc_f, wc_t, (bc.contiguous() if bc is not None else None), torch.cat([wo_f.view(d, hid), wc_f], dim=1)
-    if _pack_cache is None:
-        return build()
-    bo, b3b = param_of(w_out), param_of(w3)
-    if bo is None or b3b is None:
-        return build()
-    key = ("ffn_collapsed", id(bo), bo._version, id(b3b), b3b._version, w_out.data_ptr(), w3.data_ptr(),
-           None if b3 is None else (b3.data_ptr(), b3._version), None if b_out is None else (b_out.data_ptr(), b_out._version))
-    hit = _pack_cache.get(key)
-    if hit is None:
-        hit = _pack_cache[key] = build()
-    return hit
+    return _step_cached((w_out, w3, b3, b_out), "ffn_collapsed", build)
 
 
 def ffn_du_operand(w_out: torch.Tensor, w1: torch.Tensor) -> torch.Tensor:
@@ -675,14 +743,7 @@ def ffn_du_operand(w_out: torch.Tensor, w1: torch.Tensor) -> torch.Tensor:
         _, wo_t = pack_weight(w_out.view(d, 1, hid), False, True, False)        # bf16 [hid, 1, d]
         _, w1_t = pack_weight(w1.view(mid, 1, hid), False, True, False)         # bf16 [hid, 1, mid]
         return torch.cat([wo_t.view(hid, d), w1_t.view(hid, mid)], dim=1)
-    bo, b1 = param_of(w_out), param_of(w1)
-    if _pack_cache is None or bo is None or b1 is None:
-        return build()
-    key = ("ffn_du", id(bo), bo._version, id(b1), b1._version, w_out.data_ptr(), w1.data_ptr())
-    hit = _pack_cache.get(key)
-    if hit is None:
-        hit = _pack_cache[key] = build()
-    return hit
+    return _step_cached((w_out, w1), "ffn_du", build)
 
 
 def ffn_chain_grads(G: torch.Tensor, gs, w_out: torch.Tensor, w3: torch.Tensor, b3=None, out_w=None, out_w3=None):
@@ -769,89 +830,13 @@ def flush_deferred_grads():
                 pb3.grad = db3 if pb3.grad is None else pb3.grad.add_(db3)
 
 
-# data-gradient form of the 4x4 / stride-2 convolutions ('c4s2'): "polyphase" (2x2 footprint, phase-shuffled store) or "dilated"
-# (4x4 taps over the zero-dilated gradient); tools/gan_bench.py times both
-C4S2_DGRAD_FORM = "polyphase"
-_C4S2_KY = ((3, 1), (2, 0))    # [phase][tap] -> ky
-
-
-def _c4s2_poly_weight(w: torch.Tensor, Cout: int, Cin: int) -> torch.Tensor:
-    """w fp32 [Cout, 4, 4, Cin] -> bf16 [4*Cin, 2, 2, Cout]: row (2*py+px)*Cin + ci, tap (ty, tx) = w[co, ky(py,ty), kx(px,tx), ci]."""
-    wt = w.permute(3, 1, 2, 0)                                   # [Cin, ky, kx, Cout]
-    out = torch.empty((4, Cin, 2, 2, Cout), dtype=BF16, device=w.device)
-    for py in range(2):
-        for px in range(2):
-            sel = wt[:, list(_C4S2_KY[py])][:, :, list(_C4S2_KY[px])]
-            out[2 * py + px] = sel.to(BF16)
-    return out.view(4 * Cin, 2, 2, Cout)
-
-
 def conv_dgrad(g: _Geo, w, gz, x_shape, residual=None, aux=None, aux_act: int = 0):
-    """Gradient w.r.t. the layer input.  Optional fusions (one kernel, no extra pass):
+    """Gradient w.r.t. the layer input (forward-only modes raise).  Optional fusions (one kernel, no extra pass):
     residual: a second gradient of the same tensor to add;  aux/aux_act: multiply by act'(aux), i.e. return the
     gradient w.r.t. the pre-activation `aux` of the layer that produced this layer's input."""
-    lib = L.load()
-    m = g.mode
-    T = g.KH * g.KW
-    dev = gz.device
-    if m == "unshuf":  # GEMM rows n = (dy,dx,c): transpose the flattened [Cout, 4*Cin] matrix
-        _, wt = pack_weight(w.view(g.Cout, 1, T * g.Cin), False, True, False)
-    elif m in ("c3s2", "c3up") or (m == "c4s2" and C4S2_DGRAD_FORM == "polyphase"):
-        wt = None      # (parity / polyphase formulations below build their own operands)
-    else:              # [Cin][taps (reversed for 3x3 / 4x4)][Cout]
-        _, wt = pack_weight(w.view(g.Cout, T, g.Cin), False, True, m in ("c3s1", "c4s1", "c4s2"))
-    dx = torch.empty(x_shape, dtype=BF16, device=dev)
-    if m == "linear":
-        d = _desc(batch=g.B, h_in=1, w_in=1, c_in=g.Cout, ldx=g.Cout, h_out=1, w_out=1, c_out=g.Cin, ldo=g.Cin, kh=1, kw=1)
-        _igemm_bwd(d, gz, wt, residual, aux, aux_act, dx)
-    elif m == "c3s1":
-        d = _desc(batch=g.B, h_in=g.H, w_in=g.W, c_in=g.Cout, ldx=g.Cout, h_out=g.H, w_out=g.W, c_out=g.Cin, ldo=g.Cin,
-                  kh=3, kw=3, stride=1, pad=1)
-        _igemm_bwd(d, gz, wt, residual, aux, aux_act, dx)
-    elif m == "c3s2":   # (sizes are even: _Geo asserts it)
-        # By output parity: dx[2y+py, 2x+px] only sees the taps with ky = 1 (py = 0) or ky in {2, 0} at gz rows y, y+1
-        # (py = 1), likewise in x.  One GEMM over the low-resolution grid with a 2x2 footprint and 4*Cin columns -- class
-        # (py, px) in column quadrant 2*py+px, its unused taps zero -- stored pixel-shuffled: 16 tap-GEMMs instead of the
-        # 36 of a zero-dilated 3x3 on the full-resolution grid (9 are the algorithmic minimum).
-        wd = _derived_weight(w, "s2_parity", lambda: _s2_parity_weight(w, g.Cout, g.Cin))
-        d = _desc(batch=g.B, h_in=g.Ho, w_in=g.Wo, c_in=g.Cout, ldx=g.Cout, h_out=g.Ho, w_out=g.Wo, c_out=4 * g.Cin, ldo=g.Cin,
-                  kh=2, kw=2, stride=1, pad=0, store_shuffle=1)
-        _igemm_bwd(d, gz, wd, residual, aux, aux_act, dx)
-    elif m == "c3up":   # adjoint of the polyphase form: 4x4 / stride-2 / pad-1 convolution of the high-resolution gradient
-        wd = _derived_weight(w, "up_dgrad", lambda: _up_dgrad_weight(w, g.Cout, g.Cin))
-        d = _desc(batch=g.B, h_in=g.Ho, w_in=g.Wo, c_in=g.Cout, ldx=g.Cout, h_out=g.H, w_out=g.W, c_out=g.Cin, ldo=g.Cin,
-                  kh=4, kw=4, stride=2, pad=1)
-        _igemm_bwd(d, gz, wd, residual, aux, aux_act, dx)
-    elif m == "c4s1":   # dx[iy] = sum_ky gz[iy + 1 - ky] w[ky]: taps reversed (t = 3 - ky), gz row iy + t - 2, i.e. pad 2
-        d = _desc(batch=g.B, h_in=g.Ho, w_in=g.Wo, c_in=g.Cout, ldx=g.Cout, h_out=g.H, w_out=g.W, c_out=g.Cin, ldo=g.Cin,
-                  kh=4, kw=4, stride=1, pad=2)
-        _igemm_bwd(d, gz, wt, residual, aux, aux_act, dx)
-    elif m == "c4s2" and C4S2_DGRAD_FORM == "polyphase":
-        # The adjoint of a 4x4 / stride-2 / pad-1 convolution is the polyphase upsampling convolution of 'c3up': dx row
-        # Y = 2y - py only sees ky of one parity, at gz rows y-1 (tap 0) and y (tap 1) of cell y on the (Ho+1)-cell grid:
-        #     py = 0: tap 0 <- ky 3, tap 1 <- ky 1        py = 1: tap 0 <- ky 2, tap 1 <- ky 0        (the same along x)
-        # 4 tap-GEMMs per output pixel instead of the 16 (12 of them on zeros) of the zero-dilated form.
-        wd = _derived_weight(w, "c4s2_poly", lambda: _c4s2_poly_weight(w, g.Cout, g.Cin))
-        d = _desc(batch=g.B, h_in=g.Ho, w_in=g.Wo, c_in=g.Cout, ldx=g.Cout, h_out=g.Ho + 1, w_out=g.Wo + 1, c_out=4 * g.Cin,
-                  ldo=g.Cin, kh=2, kw=2, stride=1, pad=1, store_shuffle=2)
-        _igemm_bwd(d, gz, wd, residual, aux, aux_act, dx)
-    elif m == "c4s2":   # zero-dilated form: virtual row uy = iy + t - 2 of the dilated gradient, valid where even, gz row uy / 2
-        d = _desc(batch=g.B, h_in=g.Ho, w_in=g.Wo, c_in=g.Cout, ldx=g.Cout, h_out=g.H, w_out=g.W, c_out=g.Cin, ldo=g.Cin,
-                  kh=4, kw=4, stride=1, pad=2, up_shift=1, dil_mask=1)
-        _igemm_bwd(d, gz, wt, residual, aux, aux_act, dx)
-    elif m == "unshuf":
-        # dx[b,2oy+dy,2ox+dx,c] = sum_co gz[b,oy,ox,co] W[co,dy,dx,c]  -> GEMM with shuffled store
-        d = _desc(batch=g.B, h_in=g.Ho, w_in=g.Wo, c_in=g.Cout, ldx=g.Cout, h_out=g.Ho, w_out=g.Wo, c_out=4 * g.Cin, ldo=g.Cin,
-                  kh=1, kw=1, store_shuffle=1)
-        _igemm_bwd(d, gz, wt, residual, aux, aux_act, dx)
-    elif m == "shuf":
-        # dx[p,ci] = sum_{q,c} gz_hi[pix(p,q),c] W[(q,c),ci]  -> 2x2/stride-2 gather conv over gz_hi
-        cq = g.Cout // 4
-        d = _desc(batch=g.B, h_in=2 * g.H, w_in=2 * g.W, c_in=cq, ldx=cq, h_out=g.H, w_out=g.W, c_out=g.Cin, ldo=g.Cin,
-                  kh=2, kw=2, stride=2, pad=0)
-        _igemm_bwd(d, gz, wt, residual, aux, aux_act, dx)
-    else:
-        raise ValueError(m)
+    wt = g.dgrad_plan().operand(g, w)
+    dx = torch.empty(x_shape, dtype=BF16, device=gz.device)
+    _igemm_bwd(g.dgrad_desc(), gz, wt, residual, aux, aux_act, dx)
     return dx
 
 
@@ -901,24 +886,25 @@ def _grad_buffer(shape, device, zero: bool):
 def conv_wgrad_alloc(g: _Geo, w, need_db: bool, x=None, gz=None):
     """Outputs of conv_wgrad (allocated on the stream that will consume them), zeroed only where the kernel accumulates.
     x / gz: the operands, when the launch may be chunked (> 2 GiB): the plan is that of the first chunk."""
-    if g.mode == "shuf":
-        db = zeros_f32((g.Cout,), w.device) if need_db else None
+    db = zeros_f32((g.Cout,), w.device) if need_db else None       # (the bias gradient is always ADDED to: include/transvae_hip.h)
+    if g.md.wgrad == "transposed":
         return zeros_f32((g.Cin, 2, 2, g.Cout // 4), w.device), db
     d0 = g.fwd_desc(0)
     zero = not _wgrad_overwrites(wgrad_plan_desc(d0, x, gz) if x is not None else d0)
-    db = zeros_f32((g.Cout,), w.device) if need_db else None       # (the bias gradient is always ADDED to: include/transvae_hip.h)
     return _grad_buffer(tuple(w.shape), w.device, zero), db
 
 
 def conv_wgrad(g: _Geo, w, x, gz, need_db: bool, out=None, accumulate: bool = False):
     """(dw in w's layout, dbias | None), fp32.  `out` = buffers from conv_wgrad_alloc (optional).
-    accumulate ('c3up' only, with out = (dw, dbias | None) holding the gradients of earlier micro-batches): add in place."""
+    accumulate (where g.accumulates, with out = (dw, dbias | None) holding the gradients of earlier micro-batches): add in place."""
     dev = x.device
-    if g.mode == "c3up":
-        # weight gradient of the polyphase form = that of its adjoint conv (gathered operand: the high-resolution
-        # gradient under 4x4 / stride-2 taps; the other operand: the layer input), folded back onto the 3x3 taps
-        d = _desc(batch=g.B, h_in=g.Ho, w_in=g.Wo, c_in=g.Cout, ldx=g.Cout, h_out=g.H, w_out=g.W, c_out=g.Cin, ldo=g.Cin,
-                  kh=4, kw=4, stride=2, pad=1)
+    plan = g.md.wgrad
+    if plan == "direct":
+        dw, db = out if out is not None else conv_wgrad_alloc(g, w, need_db, x, gz)
+        wgrad(g.fwd_desc(0), x, gz, dw, db, _acc=accumulate)
+        return dw, db
+    d = g.dgrad_desc()          # the adjoint problem: gathered operand = the high-resolution gradient, the other = the layer input
+    if plan == "fold":
         d16 = _grad_buffer((g.Cin, 4, 4, g.Cout), dev, not _wgrad_overwrites(wgrad_plan_desc(d, gz, x)))
         wgrad(d, gz, x, d16, None)
         db = gz.view(-1, g.Cout).sum(0, dtype=torch.float32) if need_db else None
@@ -927,28 +913,16 @@ def conv_wgrad(g: _Geo, w, x, gz, need_db: bool, out=None, accumulate: bool = Fa
             if need_db:
                 out[1].add_(db)
             return out
-        dw = _up_fold_wgrad(d16, g.Cout, g.Cin)
-        return dw, db
-    if out is not None and g.mode != "shuf":
-        dw, db = out
-        wgrad(g.fwd_desc(0), x, gz, dw, db)
-        return dw, db
-    if g.mode != "shuf":
-        dw, db = conv_wgrad_alloc(g, w, need_db, x, gz)
-        wgrad(g.fwd_desc(0), x, gz, dw, db)
-        return dw, db
-    db = zeros_f32((g.Cout,), dev) if need_db else None
+        return _up_fold_wgrad(d16, g.Cout, g.Cin), db
+    _require(not accumulate, "this mode's weight gradient has no in-place form")
     cq = g.Cout // 4
-    d = _desc(batch=g.B, h_in=2 * g.H, w_in=2 * g.W, c_in=cq, ldx=cq, h_out=g.H, w_out=g.W, c_out=g.Cin, ldo=g.Cin,
-              kh=2, kw=2, stride=2, pad=0)
     dwt = zeros_f32((g.Cin, 2, 2, cq), dev)
-    wgrad(d, gz, x, dwt, None)     # the transposed problem: gathered operand = hi-res gradient
+    wgrad(d, gz, x, dwt, None)
     dw = dwt.permute(1, 2, 3, 0).reshape(g.Cout, 1, 1, g.Cin).contiguous()
-    if need_db:
-        d1 = _desc(batch=g.B, h_in=2 * g.H, w_in=2 * g.W, c_in=cq, ldx=cq, h_out=g.H, w_out=g.W, c_out=8, ldo=8,
-                   kh=2, kw=2, stride=2, pad=0)
+    db = None
+    if need_db:                 # the same launch against a block of ones: column sums per (quad, channel)
         tmp = zeros_f32((8, 2, 2, cq), dev)
-        wgrad(d1, gz, _ones(g.B * g.H * g.W, dev), tmp, None)
+        wgrad(_desc_like(d, c_out=8, ldo=8), gz, _ones(g.B * g.H * g.W, dev), tmp, None)
         db = tmp[0].reshape(g.Cout).contiguous()
     return dw, db
 
@@ -1005,22 +979,52 @@ def linear(x, w, bias=None, residual=None, act: Optional[str] = None):
 # ---------------------------------------------------------------------------------------------
 # GroupNorm + SiLU
 # ---------------------------------------------------------------------------------------------
+def gn_silu_fwd(x, gamma, beta, groups, eps):
+    """(silu(groupnorm(x)), [B, groups, 2] mean / rstd): a statistics pass and the apply pass"""
+    B, H, W, Cc = x.shape
+    lib = L.load()
+    stats = torch.empty((B, Cc, 2), dtype=torch.float32, device=x.device)
+    part = torch.empty((lib.tv_gn_partial_count(B, H * W, Cc),), dtype=torch.float32, device=x.device)
+    L.check(lib.tv_gn_stats(_p(x), _p(stats), _p(part), B, H * W, Cc, _stream()), "tv_gn_stats")
+    mr = torch.empty((B, groups, 2), dtype=torch.float32, device=x.device)
+    y = torch.empty_like(x)
+    L.check(lib.tv_gn_silu_fwd(_p(x), _p(stats), _p(gamma), _p(beta), _p(mr), _p(y), B, H * W, Cc, groups, eps, _stream()),
+            "tv_gn_silu_fwd")
+    return y, mr
+
+
+def gn_silu_apply(x, mr, gamma, beta, groups):
+    """silu(groupnorm(x)) recomputed from saved mean / rstd (bit-identical to gn_silu_fwd's output)."""
+    B, H, W, Cc = x.shape
+    y = torch.empty_like(x)
+    L.check(L.load().tv_gn_silu_apply(_p(x), _p(mr), _p(gamma), _p(beta), _p(y), B, H * W, Cc, groups, _stream()), "tv_gn_silu_apply")
+    return y
+
+
+def gn_silu_bwd(x, dy, dres, mr, gamma, beta, groups):
+    """(dx [+ dres], dgamma, dbeta)"""
+    B, H, W, Cc = x.shape
+    lib = L.load()
+    red = torch.empty((B, Cc, 2), dtype=torch.float32, device=x.device)
+    part = torch.empty((lib.tv_gn_partial_count(B, H * W, Cc),), dtype=torch.float32, device=x.device)
+    L.check(lib.tv_gn_silu_bwd_reduce(_p(x), _p(dy), _p(mr), _p(gamma), _p(beta), _p(red), _p(part), B, H * W, Cc, groups,
+                                      _stream()), "tv_gn_silu_bwd_reduce")
+    dx = torch.empty_like(x)
+    dg = zeros_f32((Cc,), x.device)
+    db = zeros_f32((Cc,), x.device)
+    L.check(lib.tv_gn_silu_bwd_apply(_p(x), _p(dy), _p(dres), _p(mr), _p(red), _p(gamma), _p(beta), _p(dx), _p(dg), _p(db),
+                                     B, H * W, Cc, groups, _stream()), "tv_gn_silu_bwd_apply")
+    return dx, dg, db
+
+
 class GroupNormSiluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, groups: int, eps: float):
         _need_gpu(x, gamma, beta)
         _require(x.dtype == BF16 and x.is_contiguous() and x.dim() == 4, "operand check failed: x.dtype == BF16 and x.is_contiguous() and x.dim() == 4")
-        B, H, W, Cc = x.shape
-        lib = L.load()
         gamma = gamma.contiguous()
         beta = beta.contiguous()
-        stats = torch.empty((B, Cc, 2), dtype=torch.float32, device=x.device)
-        part = torch.empty((lib.tv_gn_partial_count(B, H * W, Cc),), dtype=torch.float32, device=x.device)
-        L.check(lib.tv_gn_stats(_p(x), _p(stats), _p(part), B, H * W, Cc, _stream()), "tv_gn_stats")
-        mr = torch.empty((B, groups, 2), dtype=torch.float32, device=x.device)
-        y = torch.empty_like(x)
-        L.check(lib.tv_gn_silu_fwd(_p(x), _p(stats), _p(gamma), _p(beta), _p(mr), _p(y), B, H * W, Cc, groups, eps, _stream()),
-                "tv_gn_silu_fwd")
+        y, mr = gn_silu_fwd(x, gamma, beta, groups, eps)
         ctx.groups = groups
         ctx.save_for_backward(x, gamma, beta, mr)
         return y
@@ -1028,19 +1032,7 @@ class GroupNormSiluFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, gamma, beta, mr = ctx.saved_tensors
-        B, H, W, Cc = x.shape
-        lib = L.load()
-        gy = gy.contiguous()
-        red = torch.empty((B, Cc, 2), dtype=torch.float32, device=x.device)
-        part = torch.empty((lib.tv_gn_partial_count(B, H * W, Cc),), dtype=torch.float32, device=x.device)
-        L.check(lib.tv_gn_silu_bwd_reduce(_p(x), _p(gy), _p(mr), _p(gamma), _p(beta), _p(red), _p(part), B, H * W, Cc, ctx.groups,
-                                          _stream()), "tv_gn_silu_bwd_reduce")
-        dx = torch.empty_like(x)
-        dg = zeros_f32((Cc,), x.device)
-        db = zeros_f32((Cc,), x.device)
-        L.check(lib.tv_gn_silu_bwd_apply(_p(x), _p(gy), None, _p(mr), _p(red), _p(gamma), _p(beta), _p(dx), _p(dg), _p(db),
-                                         B, H * W, Cc, ctx.groups, _stream()), "tv_gn_silu_bwd_apply")
-        return dx, dg, db, None, None
+        return (*gn_silu_bwd(x, gy.contiguous(), None, mr, gamma, beta, ctx.groups), None, None)
 
 
 def group_norm_silu(x, gamma, beta, groups: int = 32, eps: float = 1e-5):
@@ -1050,6 +1042,24 @@ def group_norm_silu(x, gamma, beta, groups: int = 32, eps: float = 1e-5):
 # ---------------------------------------------------------------------------------------------
 # token-row norms
 # ---------------------------------------------------------------------------------------------
+def rownorm_fwd(x, w, norm, eps_rms, eps_ln):
+    """norm 0 / 1: see RowNormFn"""
+    T, Cc = x.shape
+    y = torch.empty_like(x)
+    L.check(L.load().tv_rownorm_fwd(_p(x), _p(w), _p(y), T, Cc, norm, eps_rms, eps_ln, _stream()), "tv_rownorm_fwd")
+    return y
+
+
+def rownorm_bwd(x, w, dy, dres, norm, eps_rms, eps_ln):
+    """(dx [+ dres], dw | None)"""
+    T, Cc = x.shape
+    dx = torch.empty_like(x)
+    dw = zeros_f32((Cc,), x.device) if norm == 1 else None
+    L.check(L.load().tv_rownorm_bwd(_p(x), _p(w), _p(dy), _p(dres), _p(dx), _p(dw), T, Cc, norm, eps_rms, eps_ln, _stream()),
+            "tv_rownorm_bwd")
+    return dx, dw
+
+
 class RowNormFn(torch.autograd.Function):
     """mode 0: x*rsqrt(mean x^2 + eps)           (RMSNorm; its weight is folded into the next GEMM)
     mode 1: LayerNorm-hat(RMSNorm(x)*w)        (the x-hat shared by norm_q / norm_k / norm_v)"""
@@ -1058,27 +1068,16 @@ class RowNormFn(torch.autograd.Function):
     def forward(ctx, x, w, mode: int, eps_rms: float, eps_ln: float):
         _need_gpu(x, w)
         _require(x.dtype == BF16 and x.is_contiguous() and x.dim() == 2, "operand check failed: x.dtype == BF16 and x.is_contiguous() and x.dim() == 2")
-        T, Cc = x.shape
-        lib = L.load()
         if w is not None:
             w = w.contiguous()
-        y = torch.empty_like(x)
-        L.check(lib.tv_rownorm_fwd(_p(x), _p(w), _p(y), T, Cc, mode, eps_rms, eps_ln, _stream()), "tv_rownorm_fwd")
         ctx.mode, ctx.eps = mode, (eps_rms, eps_ln)
         ctx.save_for_backward(x, w)
-        return y
+        return rownorm_fwd(x, w, mode, eps_rms, eps_ln)
 
     @staticmethod
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
-        T, Cc = x.shape
-        lib = L.load()
-        gy = gy.contiguous()
-        dx = torch.empty_like(x)
-        dw = zeros_f32((Cc,), x.device) if ctx.mode == 1 else None
-        L.check(lib.tv_rownorm_bwd(_p(x), _p(w), _p(gy), None, _p(dx), _p(dw), T, Cc, ctx.mode, ctx.eps[0], ctx.eps[1], _stream()),
-                "tv_rownorm_bwd")
-        return dx, dw, None, None, None
+        return (*rownorm_bwd(x, w, gy.contiguous(), None, ctx.mode, *ctx.eps), None, None, None)
 
 
 def rms_hat(x, eps: float = 1e-6):
