@@ -280,7 +280,7 @@ __global__ __launch_bounds__(GN_THREADS) void gn_silu_bwd_apply_kernel(const bf1
         s_be[c] = beta[c];
         s_m1[c] = s_g1[g];
         s_m2[c] = s_g2[g];
-        if (blockIdx.x == 0) {  // parameter gradients: one block per image adds its sums
+        if (blockIdx.x == 0 && dgamma) {  // parameter gradients: one block per image adds its sums (null: tv_gn_param_grads takes them)
             atomicAdd(dbeta + c, red_b[c * 2]);
             atomicAdd(dgamma + c, red_b[c * 2 + 1]);
         }
@@ -325,6 +325,20 @@ __global__ __launch_bounds__(GN_THREADS) void gn_silu_bwd_apply_kernel(const bf1
         }
         gn_st<NT>(dx + off, o);
     }
+}
+
+// deterministic parameter gradients: dbeta[c] += sum_b red[b][c][0], dgamma[c] += sum_b red[b][c][1], the images added in b order by the
+// one thread that owns the channel (tv_gn_param_grads; B rows of 2 C floats: no second level needed)
+__global__ __launch_bounds__(256) void gn_param_grads_kernel(const float* __restrict__ red, int B, int C, float* dgamma, float* dbeta) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    float s = red[c * 2], q = red[c * 2 + 1];
+    for (int b = 1; b < B; ++b) {
+        s += red[((size_t)b * C + c) * 2];
+        q += red[((size_t)b * C + c) * 2 + 1];
+    }
+    dbeta[c] = dbeta[c] + s;
+    dgamma[c] = dgamma[c] + q;
 }
 
 // ---- token-row norms -------------------------------------------------------------------------
@@ -376,19 +390,22 @@ __global__ __launch_bounds__(256) void rownorm_fwd_kernel(const bf16* __restrict
     }
 }
 
-template <int MODE, int KCH>
+// DET (tv_rownorm_bwd_det, mode 1): no atomics -- each wave stores its dwv into an LDS row of its own, the four rows are added in wave
+// order and the block's partial goes to dw[blockIdx.x][C] (the caller's scratch; tv_reduce_slices adds the blocks in order).
+template <int MODE, int KCH, bool DET = false>
 __global__ __launch_bounds__(256) void rownorm_bwd_kernel(const bf16* __restrict__ x, const float* __restrict__ w, const bf16* __restrict__ dy,
                                                           const bf16* __restrict__ dres, bf16* __restrict__ dx, float* __restrict__ dw, int T,
                                                           int C, float eps_rms, float eps_ln) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* s_dw = (float*)smem;  // [C] (mode 1)
+    float* s_dw = (float*)smem;  // [C] (mode 1); DET: [4 waves][C]
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int nch = C >> 3;
     const float inv_c = 1.0f / (float)C;
     float wv[KCH][8], dwv[KCH][8];
     if constexpr (MODE == 1) {
-        for (int i = threadIdx.x; i < C; i += 256) s_dw[i] = 0.f;
+        if constexpr (!DET)
+            for (int i = threadIdx.x; i < C; i += 256) s_dw[i] = 0.f;
         // (not rw_load_cols: on its wider loads of w the compiler packs xhat w into v_pk_mul_f32 and stops contracting
         // `su += xhat w` below, which moves the bits of dx)
 #pragma unroll
@@ -468,7 +485,19 @@ __global__ __launch_bounds__(256) void rownorm_bwd_kernel(const bf16* __restrict
         a3 = tv_wave_sum(a3) * inv_c;
         rw_store<KCH>(dx, dres, (size_t)row * C, lane, nch, [&](int k, int e, float res) { return r * (g[k][e] - xh[k][e] * a3) + res; });
     }
-    if constexpr (MODE == 1) {
+    if constexpr (MODE == 1 && DET) {
+#pragma unroll
+        for (int k = 0; k < KCH; ++k) {
+            const int ch = lane + 64 * k;
+            if (ch < nch) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) s_dw[wave * C + ch * 8 + e] = dwv[k][e];
+            }
+        }
+        __syncthreads();
+        float* dst = dw + (size_t)blockIdx.x * C;
+        for (int i = threadIdx.x; i < C; i += 256) dst[i] = ((s_dw[i] + s_dw[C + i]) + s_dw[2 * C + i]) + s_dw[3 * C + i];
+    } else if constexpr (MODE == 1) {
 #pragma unroll
         for (int k = 0; k < KCH; ++k) {
             const int ch = lane + 64 * k;
@@ -610,7 +639,7 @@ extern "C" int tv_gn_silu_bwd_apply(const void* x, const void* dy, const void* d
                                     const float* gamma, const float* beta, void* dx, float* dgamma, float* dbeta, int batch, int hw,
                                     int C, int G, void* stream) {
     if (gn_check("tv_gn_silu_bwd_apply", batch, hw, C, G)) return TV_ERR_ARG;
-    TV_CHECK_ARG(x && dy && mr && red && gamma && beta && dx && dgamma && dbeta, "tv_gn_silu_bwd_apply: null pointer");
+    TV_CHECK_ARG(x && dy && mr && red && gamma && beta && dx && (!dgamma == !dbeta), "tv_gn_silu_bwd_apply: null pointer (dgamma / dbeta: both or neither)");
     dim3 grid(tv_cdiv(hw, GN_PIX_PER_BLOCK), batch);
     if (gn_nt(batch, hw, C))
         hipLaunchKernelGGL(gn_silu_bwd_apply_kernel<true>, grid, dim3(GN_THREADS), (6 * C + 2 * G) * sizeof(float), (hipStream_t)stream,
@@ -674,5 +703,44 @@ extern "C" int tv_rownorm_bwd(const void* x, const float* w, const void* dy, con
                                (const bf16*)dres, (bf16*)dx, dw, T, C, eps_rms, eps_ln);
     });
     TV_CHECK_LAUNCH("tv_rownorm_bwd");
+    return TV_OK;
+}
+
+// ---- deterministic parameter gradients ----------------------------------------------------------------
+int tv_reduce_slices_launch(const float* part, int n_slices, long long n, long long slice_stride, float* out, int accum, hipStream_t s);   // det_reduce.hip
+
+extern "C" int tv_gn_param_grads(const float* red, int B, int C, float* dgamma, float* dbeta, void* stream) {
+    TV_CHECK_ARG(red && dgamma && dbeta && B > 0 && C > 0, "tv_gn_param_grads: bad arguments (B=%d C=%d)", B, C);
+    hipLaunchKernelGGL(gn_param_grads_kernel, dim3(tv_cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, red, B, C, dgamma, dbeta);
+    TV_CHECK_LAUNCH("tv_gn_param_grads");
+    return TV_OK;
+}
+
+// blocks of the mode-1 backward = slices of its scratch: a function of (T, C) only (C does not enter today)
+static int rownorm_bwd_grid(int T) { return min(tv_cdiv(T, 4), 256 * 4); }
+
+extern "C" long long tv_rownorm_bwd_det_scratch_bytes(int T, int C) {
+    if (T <= 0 || C <= 0) return -1;
+    return (long long)rownorm_bwd_grid(T) * C * (long long)sizeof(float);
+}
+
+extern "C" int tv_rownorm_bwd_det(const void* x, const float* w, const void* dy, const void* dres, void* dx, float* dw, int T, int C, int mode,
+                                  float eps_rms, float eps_ln, float* scratch, long long scratch_bytes, void* stream) {
+    if (mode == 0) return tv_rownorm_bwd(x, w, dy, dres, dx, dw, T, C, mode, eps_rms, eps_ln, stream);   // no parameter gradient: nothing to order
+    TV_CHECK_ARG(x && dy && dx && T > 0, "tv_rownorm_bwd_det: null pointer / empty");
+    TV_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 64 * 8 * RN_MAXCH, "tv_rownorm_bwd_det: C=%d must be a multiple of 8 and <= 2560", C);
+    TV_CHECK_ARG(mode == 1 && w && dw, "tv_rownorm_bwd_det: mode %d (mode 1 needs w and dw)", mode);
+    const int grid = rownorm_bwd_grid(T);
+    TV_CHECK_ARG(scratch && scratch_bytes >= (long long)grid * C * (long long)sizeof(float),
+                 "tv_rownorm_bwd_det: scratch of %lld bytes, %lld needed (tv_rownorm_bwd_det_scratch_bytes)", scratch_bytes,
+                 (long long)grid * C * (long long)sizeof(float));
+    rw_dispatch<1, 2, 3, 5>(tv_cdiv(C >> 3, 64), [&](auto K) {
+        constexpr int kch = decltype(K)::value;
+        hipLaunchKernelGGL((rownorm_bwd_kernel<1, kch, true>), dim3(grid), dim3(256), 4 * C * sizeof(float), (hipStream_t)stream, (const bf16*)x, w,
+                           (const bf16*)dy, (const bf16*)dres, (bf16*)dx, scratch, T, C, eps_rms, eps_ln);
+    });
+    TV_CHECK_LAUNCH("tv_rownorm_bwd_det");
+    tv_reduce_slices_launch(scratch, grid, C, C, dw, 1, (hipStream_t)stream);
+    TV_CHECK_LAUNCH("tv_rownorm_bwd_det (reduce)");
     return TV_OK;
 }

@@ -33,6 +33,7 @@
 // and because every segment stride is a multiple of 8 rows the offsets of h (16 pixels) and of the second half-step
 // (32 pixels) are the same constant for every lane, whatever the segment length.
 #include "common.h"
+#include "det.h"
 
 #include <type_traits>
 
@@ -47,6 +48,8 @@ struct Kx3Args {
     int tiles_ci, chunk_px, hw_shift, w_shift, plain;
     int xcd_order, base, ny, accum;
     unsigned x_bytes;
+    long long dw_slice, db_slice;   // DET instantiations: chunk c stores into dw + c * dw_slice, dbias + c * db_slice (wgrad_tn.hip)
+    int det;                        // host only: launch the DET instantiation
 };
 
 // physical 16-byte slot of logical chunk c in row r of a [rows][TW channels] tile: 8 consecutive rows (any first row) put
@@ -79,7 +82,10 @@ constexpr int kx_stage_bytes(int tg, int tx, int seg) { return 64 * tg * 2 + kx_
 // in an MFMA phase may always overwrite the slot of step t - 1.
 // TAPS = 3: the kx-triple of a 3x3 layer.  TAPS = 1: the same loop for a 1x1 / linear layer (one tap, no neighbour rows, no ky):
 // what remains of the design there is the ping-pong schedule and the immediate-offset reads.
-template <int TG, int TX, int NWM, int NWN, int RING, int VAR, int SEG, int TAPS = 3>
+// DET: the deterministic form (see wgrad_tn_kernel): with several pixel chunks the tile is STORED into the chunk's workspace slice, and
+// the bias sums of a (chunk, co tile) all come from the block of (ky 0, ci tile 0), which alone writes them.  M and the chunk size are
+// multiples of 64 and ny = ceil(M / chunk_px), so every chunk below ny has a K-step and reaches its stores.
+template <int TG, int TX, int NWM, int NWN, int RING, int VAR, int SEG, int TAPS = 3, bool DET = false>
 __global__ __launch_bounds__(512, 1) void wgrad_kx3_kernel(const Kx3Args p) {
     constexpr int NW = 8, BKP = 64;
     static_assert(NWM * NWN == NW, "8 waves");
@@ -234,9 +240,9 @@ __global__ __launch_bounds__(512, 1) void wgrad_kx3_kernel(const Kx3Args p) {
     // vector instructions in every step -- with ONE owner block per co tile (ky = 1, ci tile 0) that block, and with it
     // the launch (one block per CU), ran 25-30 % longer than the bias-free kernel.  Every block ADDS its share into dbias
     // with atomics (single-chunk launches too): the caller passes a zeroed dbias or one that holds a running sum.
-    const bool do_bias = p.dbias != nullptr;
-    const int nshare = TAPS * p.tiles_ci;
-    int bias_ctr = ky * p.tiles_ci + ci_tile;     // steps until this block's next turn
+    const bool do_bias = DET ? (p.dbias != nullptr && ky == 0 && ci_tile == 0) : p.dbias != nullptr;
+    const int nshare = DET ? 1 : TAPS * p.tiles_ci;
+    int bias_ctr = DET ? 0 : ky * p.tiles_ci + ci_tile;     // steps until this block's next turn
     bool own = false, own_prev = false;
     constexpr int NB = (MF + NWN - 1) / NWN;
     float bsum[NB];
@@ -392,6 +398,14 @@ __global__ __launch_bounds__(512, 1) void wgrad_kx3_kernel(const Kx3Args p) {
 
     // ---- fp32 results into dw[co][ky*3 + kx][ci]; D layout: row = (lane>>4)*4 + reg (co), col = lane&15 (ci)
     const size_t ldw = (size_t)(TAPS * TAPS) * p.c_in;
+    float* dwp = p.dw;
+    float* dbp = p.dbias;
+    if constexpr (DET) {
+        if (!p.plain) {
+            dwp += (size_t)chunk_id * p.dw_slice;
+            if (do_bias) dbp += (size_t)chunk_id * p.db_slice;
+        }
+    }
 #pragma unroll
     for (int i = 0; i < MF; ++i) {
 #pragma unroll
@@ -399,12 +413,13 @@ __global__ __launch_bounds__(512, 1) void wgrad_kx3_kernel(const Kx3Args p) {
             const int co = co0 + wm * WTG + i * 16 + g * 4 + r;
 #pragma unroll
             for (int tp = 0; tp < TAPS; ++tp) {
-                float* rowp = p.dw + (size_t)co * ldw + (size_t)(ky * TAPS + tp) * p.c_in;
+                float* rowp = dwp + (size_t)co * ldw + (size_t)(ky * TAPS + tp) * p.c_in;
 #pragma unroll
                 for (int j = 0; j < NF; ++j) {
                     const int ci = ci0 + wn * WTX + j * 16 + (lane & 15);
                     if (p.plain && !p.accum) rowp[ci] = acc[tp][i][j][r];
                     else if (p.plain) rowp[ci] += acc[tp][i][j][r];
+                    else if constexpr (DET) rowp[ci] = acc[tp][i][j][r];
                     else atomicAdd(rowp + ci, acc[tp][i][j][r]);
                 }
             }
@@ -418,7 +433,11 @@ __global__ __launch_bounds__(512, 1) void wgrad_kx3_kernel(const Kx3Args p) {
                 v += __shfl_xor(v, 16, 64);
                 v += __shfl_xor(v, 32, 64);
                 const int co = co0 + wm * WTG + i * 16 + (lane & 15);
-                if (lane < 16) atomicAdd(p.dbias + co, v);
+                if constexpr (DET) {
+                    if (lane < 16) dbp[co] = p.plain ? dbp[co] + v : v;
+                } else {
+                    if (lane < 16) atomicAdd(p.dbias + co, v);
+                }
             }
     }
 }
@@ -427,20 +446,20 @@ int g_kx3_ring = 0;     // 0 = default (4 where it fits), 3 / 4: A/B
 int g_kx3_var = -1;     // schedule variant (see the kernel); -1 = default (4 with a ring of 4)
 int g_kx3_blocks = 0;   // 0 = cost model, else target number of blocks
 
-template <int TG, int TX, int NWM, int NWN, int RING, int VAR, int SEG, int TAPS = 3>
+template <int TG, int TX, int NWM, int NWN, int RING, int VAR, int SEG, int TAPS = 3, bool DET = false>
 int kx3_launch_v(const Kx3Args& a, dim3 grid, hipStream_t s) {
     constexpr int BYTES = RING * (TAPS == 1 ? 64 * (TG + TX) * 2 : kx_stage_bytes(TG, TX, SEG));
     static_assert(BYTES <= 160 * 1024, "LDS");
     static TvPerDeviceOnce attr_once;
     if (attr_once.first()) {
-        (void)hipFuncSetAttribute((const void*)wgrad_kx3_kernel<TG, TX, NWM, NWN, RING, VAR, SEG, TAPS>, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES);
+        (void)hipFuncSetAttribute((const void*)wgrad_kx3_kernel<TG, TX, NWM, NWN, RING, VAR, SEG, TAPS, DET>, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES);
     }
-    hipLaunchKernelGGL((wgrad_kx3_kernel<TG, TX, NWM, NWN, RING, VAR, SEG, TAPS>), grid, dim3(512), BYTES, s, a);
+    hipLaunchKernelGGL((wgrad_kx3_kernel<TG, TX, NWM, NWN, RING, VAR, SEG, TAPS, DET>), grid, dim3(512), BYTES, s, a);
     return 0;
 }
 
 template <int TG, int TX, int NWM, int NWN, int RING, int SEG, int TAPS = 3>
-int kx3_launch_r(Kx3Args a, hipStream_t s, bool plan_only) {
+int kx3_launch_r(Kx3Args a, hipStream_t s, bool plan_only, TvDetCtx* det) {
     const int tiles_co = a.c_out / TG;
     a.tiles_ci = a.c_in / TX;
     const long long base = (long long)tiles_co * TAPS * a.tiles_ci;
@@ -475,12 +494,29 @@ int kx3_launch_r(Kx3Args a, hipStream_t s, bool plan_only) {
     a.chunk_px = (int)chunk;
     const int ny = (int)((a.M + chunk - 1) / chunk);
     a.plain = (ny == 1) ? 1 : 0;
+    if (det) {   // deterministic call (wgrad_tn.hip, launch()): same split, the chunks go to workspace slices
+        det->ny = ny;
+        det->dw_elems = (long long)a.c_out * (TAPS * TAPS) * a.c_in;
+        det->c_out = a.c_out;
+        det->need = tv_det_need(ny, det->dw_elems, a.c_out);
+        if (!plan_only) {
+            if (det->need > det->ws_bytes || (ny > 1 && !det->ws)) return -2;
+            a.det = (ny > 1 || a.dbias) ? 1 : 0;
+            if (ny > 1) {
+                a.dw = det->ws;
+                a.dw_slice = det->dw_elems;
+                a.db_slice = a.c_out;
+                if (a.dbias) a.dbias = det->ws + (long long)ny * det->dw_elems;
+            }
+        }
+    }
     if (plan_only) return 100 + a.plain;
     a.base = (int)base;
     a.ny = ny;
     a.xcd_order = (ny > 1 && xcd) ? 1 : 0;
     dim3 grid((unsigned)base, (unsigned)ny);
     if (a.xcd_order) grid = dim3((unsigned)(8 * base * ((ny + 7) / 8)), 1);
+    if (a.det) return kx3_launch_v<TG, TX, NWM, NWN, RING, 4, SEG, TAPS, true>(a, grid, s);   // (the schedules are bit-identical: one DET instantiation per tile)
     if constexpr (TAPS == 1) {
         if (g_kx3_var == 0) return kx3_launch_v<TG, TX, NWM, NWN, RING, 0, SEG, 1>(a, grid, s);      // (A/B)
         return kx3_launch_v<TG, TX, NWM, NWN, RING, 4, SEG, 1>(a, grid, s);
@@ -498,18 +534,18 @@ int kx3_launch_r(Kx3Args a, hipStream_t s, bool plan_only) {
 }
 
 template <int TG, int TX, int NWM, int NWN, int SEG>
-int kx3_launch_s(const Kx3Args& a, hipStream_t s, bool plan_only) {
+int kx3_launch_s(const Kx3Args& a, hipStream_t s, bool plan_only, TvDetCtx* det) {
     if constexpr (4 * kx_stage_bytes(TG, TX, SEG) <= 160 * 1024) {
-        if (g_kx3_ring != 3) return kx3_launch_r<TG, TX, NWM, NWN, 4, SEG>(a, s, plan_only);
+        if (g_kx3_ring != 3) return kx3_launch_r<TG, TX, NWM, NWN, 4, SEG>(a, s, plan_only, det);
     }
-    return kx3_launch_r<TG, TX, NWM, NWN, 3, SEG>(a, s, plan_only);
+    return kx3_launch_r<TG, TX, NWM, NWN, 3, SEG>(a, s, plan_only, det);
 }
 
 template <int TG, int TX, int NWM, int NWN>
-int kx3_launch(const Kx3Args& a, hipStream_t s, bool plan_only) {
-    if (a.w >= 64) return kx3_launch_s<TG, TX, NWM, NWN, 64>(a, s, plan_only);
-    if (a.w == 32) return kx3_launch_s<TG, TX, NWM, NWN, 32>(a, s, plan_only);
-    return kx3_launch_s<TG, TX, NWM, NWN, 16>(a, s, plan_only);
+int kx3_launch(const Kx3Args& a, hipStream_t s, bool plan_only, TvDetCtx* det) {
+    if (a.w >= 64) return kx3_launch_s<TG, TX, NWM, NWN, 64>(a, s, plan_only, det);
+    if (a.w == 32) return kx3_launch_s<TG, TX, NWM, NWN, 32>(a, s, plan_only, det);
+    return kx3_launch_s<TG, TX, NWM, NWN, 16>(a, s, plan_only, det);
 }
 
 }  // namespace
@@ -529,7 +565,7 @@ extern "C" int tv_set_wgrad_kx3(int enable, int ring, int blocks) {   // ring = 
 
 // Called by wgrad_impl (wgrad_tn.hip).  Returns -1 when the layer is not this kernel's (the caller goes on to the single-tap
 // kernel), 100 / 101 for plan_only (accumulates / overwrites), 0 after a launch.
-int tv_wgrad_kx3_try(const tv_conv_desc* d, const void* x, const void* gy, float* dw, float* dbias, hipStream_t s, bool plan_only, int accum) {
+int tv_wgrad_kx3_try(const tv_conv_desc* d, const void* x, const void* gy, float* dw, float* dbias, hipStream_t s, bool plan_only, int accum, TvDetCtx* det) {
     if (!g_kx3_enable) return -1;
     auto log2_exact = [](int v) { int sh = 0; while ((1 << sh) < v) ++sh; return ((1 << sh) == v) ? sh : -1; };
     // linear / 1x1 layers through the one-tap instantiation: nothing to share between taps, but the schedule and the
@@ -547,13 +583,13 @@ int tv_wgrad_kx3_try(const tv_conv_desc* d, const void* x, const void* gy, float
         a.x = (const bf16*)x; a.gy = (const bf16*)gy; a.dw = dw; a.dbias = dbias;
         a.M = (int)Ml; a.h = 1; a.w = 64; a.c_in = d->c_in; a.ldx = d->ldx; a.c_out = d->c_out; a.ldo = d->ldo;
         a.tiles_ci = 1; a.chunk_px = 0; a.hw_shift = 6; a.w_shift = 6; a.plain = 0;
-        a.xcd_order = 0; a.base = 1; a.ny = 1; a.accum = accum;
+        a.xcd_order = 0; a.base = 1; a.ny = 1; a.accum = accum; a.dw_slice = 0; a.db_slice = 0; a.det = 0;
         a.x_bytes = (unsigned)(Ml * d->ldx * 2);
         // A/B: tv_set_wgrad_kx3(2 + 10 t, ...): t = 1: 256 x 128 tiles, t = 2: 128 x 256 tiles where they divide the layer
         const int tsel = g_kx3_enable / 10;
-        if (tsel == 1 && d->c_out % 256 == 0 && d->c_in % 128 == 0) return kx3_launch_r<256, 128, 4, 2, 3, 64, 1>(a, s, plan_only);
-        if (tsel == 2 && d->c_out % 128 == 0 && d->c_in % 256 == 0) return kx3_launch_r<128, 256, 2, 4, 3, 64, 1>(a, s, plan_only);
-        return kx3_launch_r<192, 192, 4, 2, 3, 64, 1>(a, s, plan_only);
+        if (tsel == 1 && d->c_out % 256 == 0 && d->c_in % 128 == 0) return kx3_launch_r<256, 128, 4, 2, 3, 64, 1>(a, s, plan_only, det);
+        if (tsel == 2 && d->c_out % 128 == 0 && d->c_in % 256 == 0) return kx3_launch_r<128, 256, 2, 4, 3, 64, 1>(a, s, plan_only, det);
+        return kx3_launch_r<192, 192, 4, 2, 3, 64, 1>(a, s, plan_only, det);
     }
     const int wsh = log2_exact(d->w_out), hwsh = log2_exact(d->h_out * d->w_out);
     const long long M = (long long)d->batch * d->h_out * d->w_out;
@@ -569,10 +605,10 @@ int tv_wgrad_kx3_try(const tv_conv_desc* d, const void* x, const void* gy, float
     a.x = (const bf16*)x; a.gy = (const bf16*)gy; a.dw = dw; a.dbias = dbias;
     a.M = (int)M; a.h = d->h_out; a.w = d->w_out; a.c_in = d->c_in; a.ldx = d->ldx; a.c_out = d->c_out; a.ldo = d->ldo;
     a.tiles_ci = 1; a.chunk_px = 0; a.hw_shift = hwsh; a.w_shift = wsh; a.plain = 0;
-    a.xcd_order = 0; a.base = 1; a.ny = 1; a.accum = accum;
+    a.xcd_order = 0; a.base = 1; a.ny = 1; a.accum = accum; a.dw_slice = 0; a.db_slice = 0; a.det = 0;
     a.x_bytes = (unsigned)xbytes;
     // both shapes divide the 384 / 768 / 1536-channel layers: the 128 x 128 x 3 tile measured 3-8 % faster there
     // (tools/probes/ab_wgrad3.py: 384 @64 0.561 -> 0.544 ms, 768 @32 0.555 -> 0.541, 1536 @16 0.578 -> 0.534)
-    if (t192 && !(t128 && g_kx3_prefer128 != 2)) return kx3_launch<192, 96, 4, 2>(a, s, plan_only);
-    return kx3_launch<128, 128, 2, 4>(a, s, plan_only);
+    if (t192 && !(t128 && g_kx3_prefer128 != 2)) return kx3_launch<192, 96, 4, 2>(a, s, plan_only, det);
+    return kx3_launch<128, 128, 2, 4>(a, s, plan_only, det);
 }

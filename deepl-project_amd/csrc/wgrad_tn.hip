@@ -15,9 +15,10 @@
 // 64-byte contiguous runs per wave instruction).  The bias gradient rides along as one extra MFMA
 // against an all-ones operand in the blocks that own (tap 0, ci tile 0).
 #include "common.h"
+#include "det.h"
 
 // the kx-triple kernel for 3x3 / stride-1 layers (wgrad_kx3.hip); wgrad_impl asks it first
-int tv_wgrad_kx3_try(const tv_conv_desc* d, const void* x, const void* gy, float* dw, float* dbias, hipStream_t s, bool plan_only, int accum);
+int tv_wgrad_kx3_try(const tv_conv_desc* d, const void* x, const void* gy, float* dw, float* dbias, hipStream_t s, bool plan_only, int accum, TvDetCtx* det);
 
 #ifndef TV_WGRAD_NO_PIPE
 #define TV_WGRAD_NO_PIPE 0
@@ -39,6 +40,10 @@ struct WgradArgs {
     int xcd_order, base, ny;   // block order: see the kernel
     int accum;                 // 1: add into dw / dbias even when one block owns the tile (in-place gradient accumulation)
     unsigned x_bytes;   // FAST path: extent of x in bytes
+    // deterministic launches (DET instantiations only; tv_wgrad_tn_det): pixel chunk c stores its tile into dw + c * dw_slice
+    // and its bias sums into dbias + c * db_slice -- slices of the caller's workspace, added up in chunk order afterwards
+    long long dw_slice, db_slice;
+    int det;            // host only: launch the DET instantiation
 };
 
 // physical 16-byte slot of logical chunk c in pixel-row r of a [32][TW] tile
@@ -87,7 +92,13 @@ constexpr bool wgrad_pipe() {
     return est <= budget && est <= 216 && !TV_WGRAD_NO_PIPE;
 }
 
-template <int TG, int TX, int BKP, int NWN, bool FAST, int STAGES = 2>
+// DET: the deterministic form of a launch -- no atomics.  With more than one pixel chunk (plain == 0) chunk c
+// STORES its tile into slice c of a workspace (dw_slice / db_slice above).  The bias sums of a (chunk, co tile) come from ONE block,
+// the one of (tap 0, ci tile 0), in every K-step: the turn-taking below spreads them over taps x tiles_ci blocks, which then all
+// add into the same dbias elements.  So exactly one lane writes each (chunk, co < c_out) element of a bias slice and each
+// (chunk, co < c_out, tap, ci < c_in) element of a dw slice, and every chunk below ny has at least one K-step (chunk_px is
+// ceil(M / split) rounded up, ny = ceil(M / chunk_px)), i.e. reaches the stores: the reduce reads nothing unwritten.
+template <int TG, int TX, int BKP, int NWN, bool FAST, int STAGES = 2, bool DET = false>
 __global__ __launch_bounds__(128 * NWN, (wgrad_min_waves<TG, TX, NWN>())) void wgrad_tn_kernel(const WgradArgs p) {
     constexpr int NW = 2 * NWN;                           // waves: 2 over co x NWN over ci
     constexpr int CG = TG / 8, CX = TX / 8;               // chunks per tile row
@@ -266,9 +277,9 @@ __global__ __launch_bounds__(128 * NWN, (wgrad_min_waves<TG, TX, NWN>())) void w
     //  tiles_ci blocks of a pixel chunk that share a co tile hold the same gy fragments, so they take the K-steps in turn.
     //  Every block therefore ADDS its share into dbias with atomics, single-chunk launches included: the caller passes a
     //  zeroed dbias, or one that holds a running sum.)
-    const bool do_bias = p.dbias != nullptr;
-    const int nshare = taps * p.tiles_ci;
-    int bias_ctr = tap * p.tiles_ci + ci_tile;     // K-steps until this block's next turn
+    const bool do_bias = DET ? (p.dbias != nullptr && tap == 0 && ci_tile == 0) : p.dbias != nullptr;
+    const int nshare = DET ? 1 : taps * p.tiles_ci;
+    int bias_ctr = DET ? 0 : tap * p.tiles_ci + ci_tile;     // K-steps until this block's next turn
     bool bias_now = false;
     auto bias_turn = [&]() {     // call once per K-step, before its fragments are summed
         bias_now = do_bias && bias_ctr == 0;
@@ -438,19 +449,28 @@ __global__ __launch_bounds__(128 * NWN, (wgrad_min_waves<TG, TX, NWN>())) void w
 
     // ---- fp32 atomics into dw[co][tap][ci]; D layout: row = (lane>>4)*4+reg (co), col = lane&15 (ci)
     const size_t ldw = (size_t)taps * p.c_in;
+    float* dwp = p.dw;
+    float* dbp = p.dbias;
+    if constexpr (DET) {
+        if (!p.plain) {
+            dwp += (size_t)chunk_id * p.dw_slice;
+            if (do_bias) dbp += (size_t)chunk_id * p.db_slice;
+        }
+    }
 #pragma unroll
     for (int i = 0; i < MF; ++i) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int co = co0 + wm * WTG + i * 16 + g * 4 + r;
             if (co >= p.c_out) continue;
-            float* rowp = p.dw + (size_t)co * ldw + (size_t)tap * p.c_in;
+            float* rowp = dwp + (size_t)co * ldw + (size_t)tap * p.c_in;
 #pragma unroll
             for (int j = 0; j < NF; ++j) {
                 const int ci = ci0 + wn * WTX + j * 16 + (lane & 15);
                 if (ci < p.c_in) {
                     if (p.plain && !p.accum) rowp[ci] = acc[i][j][r];   // one pixel chunk: this block owns the tile
                     else if (p.plain) rowp[ci] += acc[i][j][r];         // ... and adds to what an earlier micro-batch left there
+                    else if constexpr (DET) rowp[ci] = acc[i][j][r];    // this chunk's slice of the workspace
                     else atomicAdd(rowp + ci, acc[i][j][r]);
                 }
             }
@@ -464,7 +484,11 @@ __global__ __launch_bounds__(128 * NWN, (wgrad_min_waves<TG, TX, NWN>())) void w
                 v += __shfl_xor(v, 16, 64);
                 v += __shfl_xor(v, 32, 64);
                 const int co = co0 + wm * WTG + i * 16 + (lane & 15);
-                if (lane < 16 && co < p.c_out) atomicAdd(p.dbias + co, v);
+                if constexpr (DET) {   // the only writer of this element: the slice is stored, dbias itself (one chunk) added to
+                    if (lane < 16 && co < p.c_out) dbp[co] = p.plain ? dbp[co] + v : v;
+                } else {
+                    if (lane < 16 && co < p.c_out) atomicAdd(p.dbias + co, v);
+                }
             }
     }
 }
@@ -480,7 +504,7 @@ int g_wgrad_xcd = 1;     // 1 = tiles of one pixel chunk share an XCD (block ord
 int g_wgrad_generic = 0; // 1 = never use the FAST staging path (A/B)
 int g_wgrad_waves = 0;   // 0 = heuristic (8 waves for the 192-wide co tile), 4 / 8 = force
 
-template <int TG, int TX, int BKP, int NWN, bool FAST, int STAGES>
+template <int TG, int TX, int BKP, int NWN, bool FAST, int STAGES, bool DET = false>
 int launch_st(const WgradArgs& a, dim3 grid, hipStream_t s) {
     constexpr int BYTES = STAGES * BKP * (TG + TX) * 2;
     constexpr int NW = 2 * NWN;
@@ -490,9 +514,9 @@ int launch_st(const WgradArgs& a, dim3 grid, hipStream_t s) {
     } else {
         static TvPerDeviceOnce attr_once;
         if (attr_once.first()) {
-            (void)hipFuncSetAttribute((const void*)wgrad_tn_kernel<TG, TX, BKP, NWN, FAST, STAGES>, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES);
+            (void)hipFuncSetAttribute((const void*)wgrad_tn_kernel<TG, TX, BKP, NWN, FAST, STAGES, DET>, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES);
         }
-        hipLaunchKernelGGL((wgrad_tn_kernel<TG, TX, BKP, NWN, FAST, STAGES>), grid, dim3(128 * NWN), BYTES, s, a);
+        hipLaunchKernelGGL((wgrad_tn_kernel<TG, TX, BKP, NWN, FAST, STAGES, DET>), grid, dim3(128 * NWN), BYTES, s, a);
         return 0;
     }
 }
@@ -501,6 +525,7 @@ int g_wgrad_stages = 0;  // 0 / 2 = two-stage ring, 3 = three stages where the t
 
 template <int TG, int TX, int BKP, int NWN, bool FAST>
 int launch_f(const WgradArgs& a, dim3 grid, hipStream_t s) {
+    if (a.det) return launch_st<TG, TX, BKP, NWN, FAST, 2, true>(a, grid, s);
     if (g_wgrad_stages == 3 && launch_st<TG, TX, BKP, NWN, FAST, 3>(a, grid, s) == 0) return 0;   // (measured 7 % slower: A/B only)
     return launch_st<TG, TX, BKP, NWN, FAST, 2>(a, grid, s);
 }
@@ -511,7 +536,7 @@ int launch_s(const WgradArgs& a, dim3 grid, hipStream_t s) {
 }
 
 template <int TG, int TX>
-int launch(const WgradArgs& a0, hipStream_t s, bool plan_only, double* t_model = nullptr) {
+int launch(const WgradArgs& a0, hipStream_t s, bool plan_only, double* t_model = nullptr, TvDetCtx* det = nullptr) {
     WgradArgs a = a0;
     const int bkp = g_wgrad_bkp ? g_wgrad_bkp : (TG == 192 ? 64 : 32);   // measured: 64 pays only where 8 waves share the tile
     const int tiles_co = (a.c_out + TG - 1) / TG;
@@ -560,6 +585,22 @@ int launch(const WgradArgs& a0, hipStream_t s, bool plan_only, double* t_model =
     const int ny = (int)((a.M + chunk - 1) / chunk);
     a.plain = (ny == 1) ? 1 : 0;
     if (t_model) *t_model = best;
+    if (det) {   // deterministic call: the split is the one above (a function of the descriptor), the chunks go to workspace slices
+        det->ny = ny;
+        det->dw_elems = (long long)a.c_out * a.kh * a.kw * a.c_in;
+        det->c_out = a.c_out;
+        det->need = tv_det_need(ny, det->dw_elems, a.c_out);
+        if (!plan_only) {
+            if (det->need > det->ws_bytes || (ny > 1 && !det->ws)) return -2;    // (never launch into a workspace that is too small)
+            a.det = (ny > 1 || a.dbias) ? 1 : 0;    // (one chunk, no bias: the default instantiation's plain store is already it)
+            if (ny > 1) {
+                a.dw = det->ws;
+                a.dw_slice = det->dw_elems;
+                a.db_slice = a.c_out;
+                if (a.dbias) a.dbias = det->ws + (long long)ny * det->dw_elems;
+            }
+        }
+    }
     if (plan_only) return 100 + a.plain;   // (distinct from the TV_ERR_* codes)
     a.base = (int)base;
     a.ny = ny;
@@ -607,7 +648,7 @@ extern "C" int tv_set_wgrad_config(int bkp, int waves, int blocks) {
 }
 
 // plan_only: no launch, returns 1 if the call would overwrite dw / dbias (single pixel chunk), 0 if it accumulates
-static int wgrad_impl(const tv_conv_desc* d, const void* x, const void* gy, float* dw, float* dbias, void* stream, bool plan_only, int accum = 0) {
+static int wgrad_impl(const tv_conv_desc* d, const void* x, const void* gy, float* dw, float* dbias, void* stream, bool plan_only, int accum = 0, TvDetCtx* det = nullptr) {
     TV_CHECK_ARG(d && (plan_only || (x && gy && dw)), "tv_wgrad_tn: null pointer");
     TV_CHECK_ARG(d->c_in > 0 && d->c_in % 8 == 0, "tv_wgrad_tn: c_in=%d must be a multiple of 8", d->c_in);
     TV_CHECK_ARG(d->c_out > 0 && d->c_out % 8 == 0, "tv_wgrad_tn: c_out=%d must be a multiple of 8", d->c_out);
@@ -634,9 +675,11 @@ static int wgrad_impl(const tv_conv_desc* d, const void* x, const void* gy, floa
     a.tiles_ci = 1; a.chunk_px = 0; a.hw_shift = -1; a.w_shift = -1; a.plain = 0; a.x_bytes = 0;
     a.xcd_order = 0; a.base = 1; a.ny = 1;
     a.accum = accum;
+    a.dw_slice = 0; a.db_slice = 0; a.det = 0;
     hipStream_t s = (hipStream_t)stream;
     if (!g_wgrad_generic && !g_wgrad_blocks) {   // 3x3 / stride-1 / pad-1 on image rows of >= 64 pixels: the kx-triple kernel (wgrad_kx3.hip)
-        const int r = tv_wgrad_kx3_try(d, x, gy, dw, dbias, s, plan_only, accum);
+        const int r = tv_wgrad_kx3_try(d, x, gy, dw, dbias, s, plan_only, accum, det);
+        if (r == -2) { tv_set_error("tv_wgrad_tn_det: workspace too small"); return TV_ERR_ARG; }
         if (r >= 0) {
             if (plan_only) return r;
             TV_CHECK_LAUNCH("tv_wgrad_tn (kx3)");
@@ -657,7 +700,7 @@ static int wgrad_impl(const tv_conv_desc* d, const void* x, const void* gy, floa
         else both192 = false;
     }
     if (use256) {
-        const int r = launch<256, 256>(a, s, plan_only);
+        const int r = launch<256, 256>(a, s, plan_only, nullptr, det);
         if (plan_only) return r;
         if (r != 0) { tv_set_error("tv_wgrad_tn: no kernel for this configuration"); return TV_ERR_ARG; }
         TV_CHECK_LAUNCH("tv_wgrad_tn");
@@ -667,13 +710,13 @@ static int wgrad_impl(const tv_conv_desc* d, const void* x, const void* gy, floa
     const bool x192 = (d->c_in % 192 == 0) && (d->c_in % 128 != 0 || g_wgrad_prefer192 || both192);
     const bool g64 = d->c_out <= 64, x64 = d->c_in <= 64;
     int r;
-    if (g192 && x192) r = launch<192, 192>(a, s, plan_only);
-    else if (g192) { if (x64) r = launch<192, 64>(a, s, plan_only); else r = launch<192, 128>(a, s, plan_only); }
-    else if (x192) { if (g64) r = launch<64, 192>(a, s, plan_only); else r = launch<128, 192>(a, s, plan_only); }
-    else if (g64 && x64) r = launch<64, 64>(a, s, plan_only);
-    else if (g64) r = launch<64, 128>(a, s, plan_only);
-    else if (x64) r = launch<128, 64>(a, s, plan_only);
-    else r = launch<128, 128>(a, s, plan_only);
+    if (g192 && x192) r = launch<192, 192>(a, s, plan_only, nullptr, det);
+    else if (g192) { if (x64) r = launch<192, 64>(a, s, plan_only, nullptr, det); else r = launch<192, 128>(a, s, plan_only, nullptr, det); }
+    else if (x192) { if (g64) r = launch<64, 192>(a, s, plan_only, nullptr, det); else r = launch<128, 192>(a, s, plan_only, nullptr, det); }
+    else if (g64 && x64) r = launch<64, 64>(a, s, plan_only, nullptr, det);
+    else if (g64) r = launch<64, 128>(a, s, plan_only, nullptr, det);
+    else if (x64) r = launch<128, 64>(a, s, plan_only, nullptr, det);
+    else r = launch<128, 128>(a, s, plan_only, nullptr, det);
     if (plan_only) return r;
     if (r != 0) { tv_set_error("tv_wgrad_tn: no kernel for this configuration"); return TV_ERR_ARG; }
     TV_CHECK_LAUNCH("tv_wgrad_tn");
@@ -692,4 +735,41 @@ extern "C" int tv_wgrad_tn_acc(const tv_conv_desc* d, const void* x, const void*
 extern "C" int tv_wgrad_tn_overwrites(const tv_conv_desc* d) {
     const int r = wgrad_impl(d, nullptr, nullptr, nullptr, nullptr, nullptr, true);
     return r >= 100 ? r - 100 : -1;
+}
+
+// ---- deterministic form ---------------------------------------------------------------------------------
+// Host arithmetic only (no tv_init, like tv_wgrad_tn_overwrites): the pixel chunks `ny` of tv_wgrad_tn_det for this descriptor and
+// the workspace it needs: ny * (c_out * kh * kw * c_in + c_out) * 4 bytes with ny > 1 -- [ny] weight slices, then [ny] bias slices,
+// whether or not a bias gradient is asked for -- and 0 with ny == 1.  `accum` does not change either number.
+extern "C" int tv_wgrad_tn_plan(const tv_conv_desc* d, int accum, int* ny, long long* workspace_bytes) {
+    TV_CHECK_ARG(ny && workspace_bytes, "tv_wgrad_tn_plan: null pointer");
+    TvDetCtx det;
+    const int r = wgrad_impl(d, nullptr, nullptr, nullptr, nullptr, nullptr, true, accum, &det);
+    if (r < 100) return r < 0 ? TV_ERR_ARG : r;
+    *ny = det.ny;
+    *workspace_bytes = det.need;
+    return TV_OK;
+}
+
+extern "C" int tv_wgrad_tn_det(const tv_conv_desc* d, const void* x, const void* gy, float* dw, float* dbias, int accum, float* workspace,
+                               long long workspace_bytes, void* stream) {
+    TV_CHECK_ARG(accum == 0 || accum == 1, "tv_wgrad_tn_det: accum=%d", accum);
+    TV_CHECK_ARG(workspace_bytes >= 0 && ((uintptr_t)workspace & 15) == 0, "tv_wgrad_tn_det: workspace must be 16-byte aligned");
+    TvDetCtx det;
+    int r = wgrad_impl(d, nullptr, nullptr, nullptr, nullptr, nullptr, true, accum, &det);
+    if (r < 100) return r < 0 ? TV_ERR_ARG : r;
+    const int ny = det.ny;
+    TV_CHECK_ARG(det.need == 0 || (workspace && workspace_bytes >= det.need), "tv_wgrad_tn_det: workspace of %lld bytes, %lld needed (tv_wgrad_tn_plan)",
+                 workspace_bytes, det.need);
+    det.ws = workspace;
+    det.ws_bytes = workspace_bytes;
+    r = wgrad_impl(d, x, gy, dw, dbias, stream, false, accum, &det);
+    if (r != TV_OK) return r;
+    if (det.ny != ny) { tv_set_error("tv_wgrad_tn_det: the plan changed between query and launch"); return TV_ERR_ARG; }
+    if (ny > 1) {
+        tv_reduce_slices_launch(workspace, ny, det.dw_elems, det.dw_elems, dw, accum, (hipStream_t)stream);
+        if (dbias) tv_reduce_slices_launch(workspace + (long long)ny * det.dw_elems, ny, det.c_out, det.c_out, dbias, 1, (hipStream_t)stream);
+        TV_CHECK_LAUNCH("tv_wgrad_tn_det (reduce)");
+    }
+    return TV_OK;
 }

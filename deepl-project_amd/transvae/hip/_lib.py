@@ -62,6 +62,12 @@ SIGNATURES = {
     "tv_wgrad_tn": (_I, [_DP, _P, _P, _P, _P, _P]),
     "tv_wgrad_tn_overwrites": (_I, [_DP]),
     "tv_wgrad_tn_acc": (_I, [_DP, _P, _P, _P, _P, _P]),
+    "tv_reduce_slices": (_I, [_P, _I, _LL, _LL, _P, _I, _P]),
+    "tv_wgrad_tn_plan": (_I, [_DP, _I, C.POINTER(_I), C.POINTER(_LL)]),
+    "tv_wgrad_tn_det": (_I, [_DP, _P, _P, _P, _P, _I, _P, _LL, _P]),
+    "tv_gn_param_grads": (_I, [_P, _I, _I, _P, _P, _P]),
+    "tv_rownorm_bwd_det_scratch_bytes": (_LL, [_I, _I]),
+    "tv_rownorm_bwd_det": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _LL, _P]),
     "tv_pack_weight": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "tv_conv3x3_derived": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "tv_gn_partial_count": (_LL, [_I, _I, _I]),

@@ -294,9 +294,91 @@ def _igemm_bwd(desc, gz, wt, residual, aux, aux_act, dx):
         _launch("tv_igemm_nt_actgrad", desc, (gz, _p(wt), residual, aux, aux_act, dx))
 
 
+# ---- deterministic mode --------------------------------------------------------------------------------------------------
+# Off (the default): split-K weight gradients, bias gradients and the norm weight gradients are combined by fp32 atomics, in an
+# order that varies from run to run.  On: the same contributors STORE their partial results into slices of a workspace and
+# tv_reduce_slices adds the slices in index order (tv_wgrad_tn_det, tv_gn_param_grads, tv_rownorm_bwd_det): the same bits on
+# every run.  What the mode does not cover: torch's own operators under autograd (torch.use_deterministic_algorithms governs
+# those), the order of a multi-GPU all-reduce, and equality across builds or split heuristics.
+_deterministic = False
+_det_ws = {}       # (device index, stream) -> grow-only fp32 workspace
+_det_last = {}     # (device index, stream) -> geometry of the last deterministic launch there
+det_stats = {"peak_bytes": 0}    # largest workspace any launch has asked for (tools/step_digest.py reports it)
+
+
+def set_deterministic(on: bool) -> None:
+    """Switch the deterministic parameter-gradient kernels on or off for every later call of this process."""
+    global _deterministic
+    _deterministic = bool(on)
+
+
+def is_deterministic() -> bool:
+    return _deterministic
+
+
+@contextlib.contextmanager
+def deterministic(on: bool = True):
+    """`with deterministic():` -- the mode for the block; the previous state comes back on exit, exceptions included."""
+    prev = _deterministic
+    set_deterministic(on)
+    try:
+        yield
+    finally:
+        set_deterministic(prev)
+
+
+def _det_key(device):
+    return (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream)
+
+
+def _det_buffer(nbytes: int, device) -> torch.Tensor:
+    """The stream's workspace, at least nbytes long.  Grow-only: once warm no call allocates.  (A buffer that is replaced is
+    freed stream-ordered by the caching allocator, behind the launches that still read it.)"""
+    key = _det_key(device)
+    buf = _det_ws.get(key)
+    if buf is None or buf.numel() * 4 < nbytes:
+        buf = torch.empty(((max(nbytes, 1 << 20) + 15) // 16 * 4,), dtype=torch.float32, device=device)
+        _det_ws[key] = buf
+    det_stats["peak_bytes"] = max(det_stats["peak_bytes"], nbytes)
+    return buf
+
+
+def det_workspace(device=None):
+    """(workspace tensor | None, info) of the current stream of `device` (default: the current device): `info` describes the
+    last deterministic launch there -- kind 'wgrad': ny slices of slice_elems floats from offset 0, then ny bias slices of
+    bias_elems floats from bias_offset (whether or not a bias gradient was asked for); kind 'rownorm': ny slices (one per
+    workgroup) of slice_elems = C floats.  ny == 1 for a weight gradient means the workspace was not used."""
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    key = _det_key(device)
+    return _det_ws.get(key), dict(_det_last.get(key, {}))
+
+
+def wgrad_det_plan(desc: L.ConvDesc, accum: bool = False):
+    """(ny, workspace bytes) of the deterministic weight gradient for this descriptor (tv_wgrad_tn_plan: host arithmetic)"""
+    ny, nbytes = C.c_int(0), C.c_longlong(0)
+    L.check(L.load().tv_wgrad_tn_plan(C.byref(desc), int(accum), C.byref(ny), C.byref(nbytes)), "tv_wgrad_tn_plan")
+    return ny.value, nbytes.value
+
+
+def _wgrad_det(desc: L.ConvDesc, x, gy, dw, dbias, acc: bool):
+    lib = L.load()
+    B = desc.batch
+    ch = _batch_chunks(B, [x, gy])
+    for i, (s, c) in enumerate(ch or ((0, B),)):
+        d = desc if ch is None else _desc_like(desc, batch=c)
+        ny, need = wgrad_det_plan(d, acc or i > 0)
+        buf = _det_buffer(need, x.device)
+        L.check(lib.tv_wgrad_tn_det(C.byref(d), _row_ptr(x, B, s), _row_ptr(gy, B, s), _p(dw), _p(dbias), int(acc or i > 0), _p(buf),
+                                    buf.numel() * 4, _stream()), "tv_wgrad_tn_det")
+        n = d.c_out * d.kh * d.kw * d.c_in
+        _det_last[_det_key(x.device)] = {"kind": "wgrad", "ny": ny, "slice_elems": n, "bias_offset": ny * n, "bias_elems": d.c_out}
+
+
 def wgrad(desc: L.ConvDesc, x, gy, dw, dbias, _acc: bool = False):
     """dw (and dbias) of one layer.  Chunked launches: the first chunk follows the kernel's own overwrite / accumulate
     plan for ITS geometry (callers size-check with wgrad_plan_desc), later chunks add."""
+    if _deterministic:
+        return _wgrad_det(desc, x, gy, dw, dbias, _acc)
     _launch("tv_wgrad_tn_acc" if _acc else "tv_wgrad_tn", desc, (x, gy, _p(dw), _p(dbias)), later="tv_wgrad_tn_acc")
 
 
@@ -845,6 +927,8 @@ def _wgrad_overwrites(desc: L.ConvDesc) -> bool:
     NOT covered by the answer: it is always ADDED to with fp32 atomics (include/transvae_hip.h) and must be passed zeroed or
     holding a running sum.  The answer follows the kernel's split-K choice (and its tuning hooks), so the library is asked
     every time."""
+    if _deterministic:      # tv_wgrad_tn_det writes dw = S (one chunk: plain stores; several: the slice reduce) unless asked to add
+        return True
     r = L.load().tv_wgrad_tn_overwrites(C.byref(desc))
     if r < 0:
         raise RuntimeError("tv_wgrad_tn_overwrites: bad descriptor")
@@ -1012,6 +1096,11 @@ def gn_silu_bwd(x, dy, dres, mr, gamma, beta, groups):
     dx = torch.empty_like(x)
     dg = zeros_f32((Cc,), x.device)
     db = zeros_f32((Cc,), x.device)
+    if _deterministic:      # dx as ever; the parameter gradients from the same `red` rows, the images added in order
+        L.check(lib.tv_gn_silu_bwd_apply(_p(x), _p(dy), _p(dres), _p(mr), _p(red), _p(gamma), _p(beta), _p(dx), None, None,
+                                         B, H * W, Cc, groups, _stream()), "tv_gn_silu_bwd_apply")
+        L.check(lib.tv_gn_param_grads(_p(red), B, Cc, _p(dg), _p(db), _stream()), "tv_gn_param_grads")
+        return dx, dg, db
     L.check(lib.tv_gn_silu_bwd_apply(_p(x), _p(dy), _p(dres), _p(mr), _p(red), _p(gamma), _p(beta), _p(dx), _p(dg), _p(db),
                                      B, H * W, Cc, groups, _stream()), "tv_gn_silu_bwd_apply")
     return dx, dg, db
@@ -1055,6 +1144,14 @@ def rownorm_bwd(x, w, dy, dres, norm, eps_rms, eps_ln):
     T, Cc = x.shape
     dx = torch.empty_like(x)
     dw = zeros_f32((Cc,), x.device) if norm == 1 else None
+    if _deterministic and norm == 1:
+        lib = L.load()
+        need = lib.tv_rownorm_bwd_det_scratch_bytes(T, Cc)
+        buf = _det_buffer(need, x.device)
+        L.check(lib.tv_rownorm_bwd_det(_p(x), _p(w), _p(dy), _p(dres), _p(dx), _p(dw), T, Cc, norm, eps_rms, eps_ln, _p(buf),
+                                       buf.numel() * 4, _stream()), "tv_rownorm_bwd_det")
+        _det_last[_det_key(x.device)] = {"kind": "rownorm", "ny": need // (4 * Cc), "slice_elems": Cc}
+        return dx, dw
     L.check(L.load().tv_rownorm_bwd(_p(x), _p(w), _p(dy), _p(dres), _p(dx), _p(dw), T, Cc, norm, eps_rms, eps_ln, _stream()),
             "tv_rownorm_bwd")
     return dx, dw

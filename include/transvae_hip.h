@@ -154,6 +154,25 @@ int tv_wgrad_tn_overwrites(const tv_conv_desc* d);
  * loss.backward() into .grad). */
 int tv_wgrad_tn_acc(const tv_conv_desc* d, const void* x, const void* gy, float* dw, float* dbias, void* stream);
 
+/* Deterministic parameter gradients (csrc/det_reduce.hip): no atomics, the same bits on every run.
+ * Every contributor of a sum STORES its partial result into a slice of its own in a caller-provided fp32 workspace; the
+ * slice reduce then adds the slices in ascending index,
+ *     S[i] = fl(...fl(fl(P_0[i] + P_1[i]) + P_2[i])... + P_{n_slices-1}[i]),   P_s = part + s * slice_stride,
+ * and writes out[i] = S[i] (accum = 0) or fl(out[i] + S[i]) (accum = 1).  n >= 1 elements, slice_stride >= n. */
+int tv_reduce_slices(const float* part, int n_slices, long long n, long long slice_stride, float* out, int accum,
+                     void* stream);
+/* The split of the deterministic weight gradient for this descriptor: *ny pixel chunks, and the workspace it needs,
+ *     *workspace_bytes = ny * (c_out * kh * kw * c_in + c_out) * 4     with ny > 1   ([ny] weight slices, then [ny] bias slices)
+ *     *workspace_bytes = 0                                             with ny == 1 (one block owns every tile: plain stores).
+ * Host arithmetic only (no device is touched), the same answer on every call; `accum` changes neither number. */
+int tv_wgrad_tn_plan(const tv_conv_desc* d, int accum, int* ny, long long* workspace_bytes);
+/* tv_wgrad_tn (accum = 0: dw is written) / tv_wgrad_tn_acc (accum = 1: dw is added to) in deterministic form.  Chunk c's
+ * tile goes to slice c of `workspace` (16-byte aligned), tv_reduce_slices adds the slices into dw in chunk order; dbias
+ * -- always added to -- gets a slice per chunk the same way, summed by one workgroup per (chunk, 16 output channels).
+ * Refuses (TV_ERR_ARG) a workspace smaller than tv_wgrad_tn_plan's answer.  dw needs no zeroing with accum = 0. */
+int tv_wgrad_tn_det(const tv_conv_desc* d, const void* x, const void* gy, float* dw, float* dbias, int accum,
+                    float* workspace, long long workspace_bytes, void* stream);
+
 /*
  * fp32 -> bf16 weight repack.  src: [O, T, I] fp32 (T = kh*kw taps).
  *   dst   : [O, T, I] bf16 (forward operand)                      or NULL
@@ -197,10 +216,14 @@ int tv_gn_silu_apply(const void* x, const float* mr, const float* gamma, const f
 int tv_gn_silu_bwd_reduce(const void* x, const void* dy, const float* mr, const float* gamma,
                           const float* beta, float* red, float* partials, int batch, int hw, int C,
                           int G, void* stream);
-/* backward pass 2: dx (+= dres if given); dgamma/dbeta (fp32 [C]) accumulated from red */
+/* backward pass 2: dx (+= dres if given); dgamma/dbeta (fp32 [C]) accumulated from red with fp32 atomics -- or both null: the
+ * parameter gradients are left to tv_gn_param_grads */
 int tv_gn_silu_bwd_apply(const void* x, const void* dy, const void* dres, const float* mr,
                          const float* red, const float* gamma, const float* beta, void* dx,
                          float* dgamma, float* dbeta, int batch, int hw, int C, int G, void* stream);
+/* deterministic parameter gradients of GroupNorm+SiLU from red [B][C][2] (tv_gn_silu_bwd_reduce): dbeta[c] += sum_b red[b][c][0],
+ * dgamma[c] += sum_b red[b][c][1], the images added in b order */
+int tv_gn_param_grads(const float* red, int B, int C, float* dgamma, float* dbeta, void* stream);
 
 /* Token-wise norms (R/transvae/modules/blocks.py:179-194, attention.py:39-41,71-73) ------------
  * mode 0: y = x * rsqrt(mean(x^2)+eps_rms)                     (RMSNorm, weight folded downstream)
@@ -213,6 +236,13 @@ int tv_rownorm_fwd(const void* x, const float* w, void* y, int T, int C, int mod
 /* dx (+= dres if given) and, mode 1, dw[C] += ...  (fp32 atomics) */
 int tv_rownorm_bwd(const void* x, const float* w, const void* dy, const void* dres, void* dx,
                    float* dw, int T, int C, int mode, float eps_rms, float eps_ln, void* stream);
+/* tv_rownorm_bwd in deterministic form: each workgroup stores its partial weight gradient (its waves added in wave order) into
+ * scratch[block][C], tv_reduce_slices adds the workgroups in order into dw (added to, as above).  The number of workgroups is a
+ * function of (T, C) alone: tv_rownorm_bwd_det_scratch_bytes(T, C) is the scratch it needs; a smaller one is refused. */
+long long tv_rownorm_bwd_det_scratch_bytes(int T, int C);
+int tv_rownorm_bwd_det(const void* x, const float* w, const void* dy, const void* dres, void* dx, float* dw, int T,
+                       int C, int mode, float eps_rms, float eps_ln, float* scratch, long long scratch_bytes,
+                       void* stream);
 
 /* RoPE (R/transvae/modules/attention.py:132-199), in place on the q and k thirds of
  * qkv [B, N, 3, heads, 64] bf16.  tab: [N, 4, 32] fp32 = cos1,sin1,cos2,sin2 per pair.
