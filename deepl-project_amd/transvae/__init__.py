@@ -32,15 +32,16 @@ returns gFID, Inception Score (`InceptionScore`) and the k-NN precision / recall
 `precision_recall`) against a `reference_statistics` dict; `ParamEMA` (transvae/optim.py) is the weight average they are measured on,
 kept by `fit_dit(..., ema_decay=...)`.  `LightningDiT` / `create_lightning_dit` (transvae/lightning_dit.py, csrc/lightning.hip, csrc/dit.hip)
 are the same model with the LightningDiT block: RMSNorm adaLN with a learned weight, per-head qk-norm before the RoPE and a SwiGLU MLP,
-each behind a switch; the training, sampling and evaluation entry points above take it unchanged.  `with transvae.deterministic():`
+each behind a switch; the training, sampling and evaluation entry points above take it unchanged.  `dit_xl` / `lightning_dit_xl` are
+the XL configurations (1152 wide, 28 deep, 16 heads of head_dim 72: csrc/attention_hd.hip).  `with transvae.deterministic():`
 (transvae/hip/ops.py, csrc/det_reduce.hip) makes every parameter gradient of the HIP kernels bit-reproducible from run to run.
 """
-from .dit import DiT, create_dit, fit_dit, flow_matching_loss, sample_images, sample_latents
+from .dit import DiT, create_dit, dit_xl, fit_dit, flow_matching_loss, sample_images, sample_latents
 from .evaluate import evaluate
 from .evaluate_dit import evaluate_dit
 from .hip.ops import deterministic
 from .generate import interpolate_latents, random_samples, reconstruct
-from .lightning_dit import LightningDiT, create_lightning_dit
+from .lightning_dit import LightningDiT, create_lightning_dit, lightning_dit_xl
 from .latents import LatentStats, extract_latents, latent_density_metrics, latent_points, latent_space_metrics
 from .image_io import ImagePrep, UInt8Batch, collate_uint8, save_image, to_uint8_grid
 from .losses.lpips import PerceptualLoss
@@ -61,4 +62,4 @@ __all__ = ["TransVAE", "create_transvae", "TransVAELoss", "reconstruction_metric
            "extract_latents", "latent_points", "latent_density_metrics", "latent_space_metrics", "probe_rows", "softmax_xent", "LinearProbe",
            "fit_linear_probe", "linear_probe_accuracy", "DiT", "create_dit", "flow_matching_loss", "sample_latents", "sample_images", "fit_dit",
            "evaluate_dit", "InceptionScore", "knn_radius", "manifold_hits", "precision_recall", "reference_statistics", "ParamEMA",
-           "LightningDiT", "create_lightning_dit", "deterministic"]
+           "LightningDiT", "create_lightning_dit", "deterministic", "dit_xl", "lightning_dit_xl"]

@@ -4,7 +4,7 @@ The reference names the stage only (`train_dit.py` / `evaluate_dit.py`, both TOD
 (DESIGN.md section 3.4).  What runs where:
 
     token GEMMs        patch embedding, qkv, proj, fc1 + GELU, fc2, final linear     `ops.linear` (tv_igemm_nt / tv_wgrad_tn)
-    attention          2-D RoPE in place, flash attention, head_dim 64              `ops.attention`
+    attention          2-D RoPE in place, flash attention, head_dim 64 or 72         `ops.attention`
     conditioning rows  adaLN (LayerNorm-hat, 1 + scale, shift), gate + residual      `adaln` / `gate_residual` (csrc/dit.hip)
     flow-matching edge x_t rows from latents, loss + gradient, Euler step            `flow_rows` / `flow_loss` / `flow_euler`
     conditioning path  timestep sinusoid + MLP, label embedding, SiLU, the adaLN_modulation linears: B rows, 1/N of the token
@@ -319,15 +319,17 @@ class DiT(nn.Module):
 
     def __init__(self, input_size=16, patch_size: int = 1, in_channels: int = 32, hidden_size: int = 768, depth: int = 12,
                  num_classes: int = 1000, mlp_ratio: float = 4.0, class_dropout_prob: float = 0.1, use_rope: bool = True,
-                 frequency_embedding_size: int = 256, generator: Optional[torch.Generator] = None):
+                 frequency_embedding_size: int = 256, generator: Optional[torch.Generator] = None, head_dim: int = 64):
         super().__init__()
         h, w = _grid_of(input_size)
         if patch_size not in (1, 2):
             raise ValueError(f"DiT: patch_size={patch_size} must be 1 or 2")
         if h < 1 or w < 1 or h % patch_size or w % patch_size:
             raise ValueError(f"DiT: input_size={(h, w)} is not divisible by patch_size={patch_size}")
-        if hidden_size < 64 or hidden_size % 64:
-            raise ValueError(f"DiT: hidden_size={hidden_size} must be a multiple of head_dim = 64, the only head_dim of the attention kernels")
+        if head_dim not in (64, 72):
+            raise ValueError(f"DiT: head_dim={head_dim} must be 64 or 72, the head dimensions of the attention kernels")
+        if hidden_size < head_dim or hidden_size % head_dim:
+            raise ValueError(f"DiT: hidden_size={hidden_size} must be a multiple of head_dim = {head_dim}")
         if not use_rope:
             raise ValueError("DiT: use_rope=False is not supported: positions are 2-D RoPE only, there is no absolute position table")
         if in_channels < 1 or depth < 1 or num_classes < 1:
@@ -339,7 +341,8 @@ class DiT(nn.Module):
             raise ValueError(f"DiT: mlp_ratio={mlp_ratio} gives an inner width {inner} that is no multiple of 32")
         self.input_size, self.patch_size, self.in_channels = (h, w), int(patch_size), int(in_channels)
         self.hidden_size, self.depth, self.num_classes = int(hidden_size), int(depth), int(num_classes)
-        self.num_heads, self.class_dropout_prob, self.use_rope = hidden_size // 64, float(class_dropout_prob), True
+        self.head_dim, self.attn_scale = int(head_dim), float(head_dim) ** -0.5          # (0.125 exactly at 64)
+        self.num_heads, self.class_dropout_prob, self.use_rope = hidden_size // head_dim, float(class_dropout_prob), True
         self.grid = (h // patch_size, w // patch_size)
         self.tokens = self.grid[0] * self.grid[1]
         self.patch_cols = patch_size * patch_size * in_channels
@@ -349,7 +352,7 @@ class DiT(nn.Module):
         self.y_embedder = _Labels(num_classes, hidden_size)
         self.blocks = nn.ModuleList([DiTBlock(hidden_size, mlp_ratio) for _ in range(depth)])
         self.final_layer = _Final(hidden_size, self.patch_cols)
-        object.__setattr__(self, "_rope", RoPE2D(64))          # a table builder, kept out of the state dict
+        object.__setattr__(self, "_rope", RoPE2D(head_dim))          # a table builder, kept out of the state dict
         self.initialize_weights(generator)
 
     def _apply(self, fn, *a, **k):
@@ -425,7 +428,7 @@ class DiT(nn.Module):
             sink = ModGrad(6) if mod.requires_grad else None
             a, hs = adaln(h, mod, 0, C, N, LN_EPS, sink, True)
             qkv = ops.linear(a, blk.attn.qkv.weight, blk.attn.qkv.bias)
-            o = ops.attention(qkv.view(B, N, 3 * C), tab, self.num_heads, 0.125)
+            o = ops.attention(qkv.view(B, N, 3 * C), tab, self.num_heads, self.attn_scale, self.head_dim)
             a = ops.linear(o.view(B * N, C), blk.attn.proj.weight, blk.attn.proj.bias)
             h = gate_residual(hs, a, mod, 2 * C, N, sink)
             a, hs = adaln(h, mod, 3 * C, 4 * C, N, LN_EPS, sink, False)
@@ -449,12 +452,17 @@ def state_dict_keys(depth: int) -> list:
 
 
 def create_dit(name: str = "DiT-B", input_size=16, patch_size: int = 1, in_channels: int = 32, num_classes: int = 1000, **kwargs) -> DiT:
-    """`DiT-S` (384 wide, 12 deep), `DiT-B` (768, 12) or `DiT-L` (1024, 24).  DiT-XL (1152 = 16 heads of 72) is not offered:
-    head_dim is 64 here."""
+    """`DiT-S` (384 wide, 12 deep), `DiT-B` (768, 12) or `DiT-L` (1024, 24), all at head_dim 64.  DiT-XL (1152 wide, 28 deep, 16 heads
+    of 72) is `dit_xl`."""
     if name not in PRESETS:
         raise ValueError(f"create_dit: name={name!r} is not one of {sorted(PRESETS)}")
     hidden, depth = PRESETS[name]
     return DiT(input_size, patch_size, in_channels, hidden, depth, num_classes, **kwargs)
+
+
+def dit_xl(input_size=16, patch_size: int = 1, in_channels: int = 32, num_classes: int = 1000, **kwargs) -> DiT:
+    """DiT-XL: 1152 wide, 28 deep, 16 heads of head_dim 72 (the attention kernels of csrc/attention_hd.hip)."""
+    return DiT(input_size, patch_size, in_channels, 1152, 28, num_classes, head_dim=72, **kwargs)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -154,6 +154,12 @@ SIGNATURES = {
     "tv_qknorm_rope_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
     "tv_swiglu_fwd": (_I, [_P, _P, _LL, _I, _P]),
     "tv_swiglu_bwd": (_I, [_P, _P, _P, _LL, _I, _P]),
+    "tv_attn_fwd_hd": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "tv_attn_bwd_hd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "tv_rope_qk_hd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "tv_qknorm_rope_fwd_hd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "tv_qknorm_rope_bwd_hd_partial_count": (_LL, [_I, _I, _I, _I]),
+    "tv_qknorm_rope_bwd_hd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "tv_knn_radius": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "tv_manifold_hits": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P]),
     "tv_softmax_stats": (_I, [_P, _I, _I, _I, _P, _P, _P]),
@@ -182,7 +188,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     # -fno-slp-vectorize: the SLP pass packs the softmax's multiplies / adds into v_pk_*_f32 on MISALIGNED register pairs
     # and pays for it with v_mov / v_perm / v_alignbit shuffles (dk/dv loop: 16 v_mul became 8 v_pk_mul + 14 moves), and
     # packed fp32 is slower than two scalar operations next to MFMAs anyway (MI355X guide, cycle constants)
-    extra = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize"]}
+    extra = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize"],
+             "attention_hd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}   # (the same softmax on MFMA results; SLP not measured there)
     procs = []
     objs = []
     for s in srcs:

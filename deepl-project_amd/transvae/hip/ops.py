@@ -1186,7 +1186,7 @@ def rms_ln_hat(x, w, eps_rms: float = 1e-6, eps_ln: float = 1e-5):
 
 
 # ---------------------------------------------------------------------------------------------
-# attention (RoPE + flash attention, head_dim 64)
+# attention (RoPE + flash attention; head_dim 64, and 72 through the tv_*_hd entries)
 # ---------------------------------------------------------------------------------------------
 class AttentionFn(torch.autograd.Function):
     """qkv: [B, N, 3*C] bf16 (q | k | v, each [heads, 64]); returns o [B, N, C].
@@ -1228,8 +1228,50 @@ class AttentionFn(torch.autograd.Function):
         return dqkv, None, None, None
 
 
-def attention(qkv, rope_tab, heads: int, scale: float):
-    return AttentionFn.apply(qkv, rope_tab, heads, scale)
+class AttentionHdFn(torch.autograd.Function):
+    """`AttentionFn` at head_dim 72 (csrc/attention_hd.hip): qkv [B, N, 3*C] bf16 (q | k | v, each [heads, 72]), table [N, 4, 36].
+
+    RoPE is applied IN PLACE on the q and k thirds of `qkv`; the backward hands the table to tv_attn_bwd_hd, which stores dq / dk
+    as gradients of the un-rotated projections (the adjoint on the fp32 sums, one rounding)."""
+
+    @staticmethod
+    def forward(ctx, qkv, rope_tab, heads: int, scale: float, head_dim: int):
+        _need_gpu(qkv)
+        _require(qkv.dtype == BF16 and qkv.is_contiguous() and qkv.dim() == 3, "operand check failed: qkv.dtype == BF16 and qkv.is_contiguous() and qkv.dim() == 3")
+        B, N, C3 = qkv.shape
+        _require(C3 == 3 * heads * head_dim, f"operand check failed: C3 == 3 * heads * head_dim (head_dim = {head_dim})")
+        lib = L.load()
+        if rope_tab is not None:
+            _require(rope_tab.dtype == torch.float32 and rope_tab.shape == (N, 4, head_dim // 2) and rope_tab.is_contiguous() and
+                     rope_tab.device == qkv.device, f"operand check failed: rope_tab contiguous fp32 (N, 4, {head_dim // 2}) on the rows' device")
+            L.check(lib.tv_rope_qk_hd(_p(qkv), _p(rope_tab), B, N, heads, head_dim, 0, _stream()), "tv_rope_qk_hd")
+        o = torch.empty((B, N, heads * head_dim), dtype=BF16, device=qkv.device)
+        lse = torch.empty((B, heads, N), dtype=torch.float32, device=qkv.device)
+        L.check(lib.tv_attn_fwd_hd(_p(qkv), _p(o), _p(lse), B, N, heads, head_dim, scale, _stream()), "tv_attn_fwd_hd")
+        ctx.args = (heads, scale, head_dim)
+        ctx.save_for_backward(qkv, o, lse, rope_tab)
+        return o
+
+    @staticmethod
+    def backward(ctx, go):
+        qkv, o, lse, rope_tab = ctx.saved_tensors
+        B, N, _ = qkv.shape
+        heads, scale, head_dim = ctx.args
+        go = go.contiguous()
+        delta = torch.empty((2, B, heads, N), dtype=torch.float32, device=qkv.device)   # scratch: -delta, -lse log2(e)
+        dqkv = torch.empty_like(qkv)
+        L.check(L.load().tv_attn_bwd_hd(_p(qkv), _p(o), _p(go), _p(lse), _p(delta), _p(rope_tab), _p(dqkv), B, N, heads, head_dim, scale,
+                                        _stream()), "tv_attn_bwd_hd")
+        return dqkv, None, None, None, None
+
+
+def attention(qkv, rope_tab, heads: int, scale: float, head_dim: int = 64):
+    """RoPE + flash attention.  `head_dim` is 64 or 72 and is never inferred from the shapes: 72 takes the kernels of
+    csrc/attention_hd.hip and a table [N, 4, 36]."""
+    if head_dim == 64:
+        return AttentionFn.apply(qkv, rope_tab, heads, scale)
+    _require(head_dim == 72, f"attention: head_dim={head_dim} must be 64 or 72")
+    return AttentionHdFn.apply(qkv, rope_tab, int(heads), float(scale), 72)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -7,8 +7,9 @@ a TODO there).  `LightningDiT` is `DiT` with three switches, each of which repla
     use_qknorm    per-head RMSNorm of q and k before the 2-D RoPE                                   `qk_norm_rope_attention`
     use_swiglu    w3(silu(x1) x2), [x1 | x2] = w12(x), inner width (2 int(C mlp_ratio)) // 3         `swiglu`
 
-`adaln_rms` is the RMS form of the adaLN kernel pair in csrc/dit.hip, the other two pairs are csrc/lightning.hip; everything else
-(embedders, conditioning path, padding, RoPE table, token GEMMs, attention, gate + residual, the flow-matching edge,
+`adaln_rms` is the RMS form of the adaLN kernel pair in csrc/dit.hip, the other two pairs are csrc/lightning.hip (the qk-norm pair at
+head_dim 72, `LightningDiT(..., head_dim=72)` / `lightning_dit_xl`, is csrc/attention_hd.hip); everything else
+(embedders, conditioning path, padding, RoPE table, token GEMMs, attention at head_dim 64 or 72, gate + residual, the flow-matching edge,
 `flow_matching_loss` / `sample_latents` / `fit_dit` / `evaluate_dit`) is what `DiT` uses, unchanged.  With a switch off that part of the
 block is the DiT path.  There is no CPU fallback: host tensors raise.
 """
@@ -81,6 +82,51 @@ class _QkNormRopeAttnFn(torch.autograd.Function):
         return dqkv, dwq, dwk, None, None, None, None, None
 
 
+class _QkNormRopeAttnHdFn(torch.autograd.Function):
+    """`_QkNormRopeAttnFn` at head_dim 72: the tv_*_hd entries of csrc/attention_hd.hip, weights [72], table [N, 4, 36]."""
+
+    @staticmethod
+    def forward(ctx, qkv, wq, wk, rope_tab, heads, scale, eps, keep_raw, hd):
+        ops._need_gpu(qkv)
+        ops._require(qkv.dtype == torch.bfloat16 and qkv.is_contiguous() and qkv.dim() == 3, "qk_norm_rope_attention: contiguous bf16 qkv [B, N, 3 C]")
+        B, N, C3 = qkv.shape
+        ops._require(C3 == 3 * heads * hd, f"qk_norm_rope_attention: the last axis must be 3 * heads * head_dim (head_dim = {hd})")
+        _check_weight(wq, hd, qkv, "qk_norm_rope_attention: q_norm")
+        _check_weight(wk, hd, qkv, "qk_norm_rope_attention: k_norm")
+        if rope_tab is not None:
+            ops._require(rope_tab.dtype == torch.float32 and tuple(rope_tab.shape) == (N, 4, hd // 2) and rope_tab.is_contiguous() and
+                         rope_tab.device == qkv.device, f"qk_norm_rope_attention: the RoPE table must be contiguous fp32 [N, 4, {hd // 2}]")
+        lib = L.load()
+        qn = torch.empty_like(qkv) if keep_raw else qkv          # in place when no backward will ask for the raw projections
+        L.check(lib.tv_qknorm_rope_fwd_hd(ops._p(qkv), ops._p(wq), ops._p(wk), ops._p(rope_tab), ops._p(qn), B, N, heads, hd, eps, ops._stream()),
+                "tv_qknorm_rope_fwd_hd")
+        o = torch.empty((B, N, heads * hd), dtype=torch.bfloat16, device=qkv.device)
+        lse = torch.empty((B, heads, N), dtype=torch.float32, device=qkv.device)
+        L.check(lib.tv_attn_fwd_hd(ops._p(qn), ops._p(o), ops._p(lse), B, N, heads, hd, scale, ops._stream()), "tv_attn_fwd_hd")
+        ctx.args = (heads, scale, eps, hd)
+        if keep_raw:
+            ctx.save_for_backward(qkv, qn, o, lse, wq, wk, rope_tab)
+        return o
+
+    @staticmethod
+    def backward(ctx, go):
+        qkv, qn, o, lse, wq, wk, rope_tab = ctx.saved_tensors
+        heads, scale, eps, hd = ctx.args
+        B, N, _ = qkv.shape
+        lib = L.load()
+        go = go.contiguous()
+        ops._require(go.dtype == torch.bfloat16, "qk_norm_rope_attention: bf16 gradient rows")
+        delta = torch.empty((2, B, heads, N), dtype=torch.float32, device=qkv.device)   # scratch: -delta, -lse log2(e)
+        dqkv = torch.empty_like(qkv)
+        L.check(lib.tv_attn_bwd_hd(ops._p(qn), ops._p(o), ops._p(go), ops._p(lse), ops._p(delta), ops._p(rope_tab), ops._p(dqkv), B, N, heads, hd,
+                                   scale, ops._stream()), "tv_attn_bwd_hd")
+        dwq, dwk = torch.empty_like(wq), torch.empty_like(wk)
+        part = torch.empty(lib.tv_qknorm_rope_bwd_hd_partial_count(B, N, heads, hd), dtype=torch.float32, device=qkv.device)
+        L.check(lib.tv_qknorm_rope_bwd_hd(ops._p(qkv), ops._p(wq), ops._p(wk), ops._p(dqkv), ops._p(dwq), ops._p(dwk), ops._p(part), B, N, heads, hd,
+                                          eps, ops._stream()), "tv_qknorm_rope_bwd_hd")
+        return dqkv, dwq, dwk, None, None, None, None, None, None
+
+
 class _SwiGLUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u):
@@ -114,12 +160,16 @@ def adaln_rms(x: torch.Tensor, weight: torch.Tensor, mod: torch.Tensor, shift_of
 
 
 def qk_norm_rope_attention(qkv: torch.Tensor, q_weight: torch.Tensor, k_weight: torch.Tensor, rope_tab: Optional[torch.Tensor], heads: int,
-                           scale: float, eps: float = LN_EPS) -> torch.Tensor:
-    """Attention on qkv [B, N, 3 C] bf16 (q | k | v, each [heads, 64]) with a per-head RMSNorm of q and k (fp32 weights [64]) before
-    the 2-D RoPE; returns o [B, N, C].  When no gradient is wanted (`torch.no_grad()`, or nothing that requires one) the norm and
-    the rotation run IN PLACE on `qkv`, which the caller must not reuse; otherwise the raw projections are kept for the backward."""
+                           scale: float, eps: float = LN_EPS, head_dim: int = 64) -> torch.Tensor:
+    """Attention on qkv [B, N, 3 C] bf16 (q | k | v, each [heads, head_dim]) with a per-head RMSNorm of q and k (fp32 weights
+    [head_dim]) before the 2-D RoPE; returns o [B, N, C].  When no gradient is wanted (`torch.no_grad()`, or nothing that requires
+    one) the norm and the rotation run IN PLACE on `qkv`, which the caller must not reuse; otherwise the raw projections are kept
+    for the backward.  `head_dim` is 64 or 72 (never inferred from the shapes); 72 takes a table [N, 4, 36]."""
     keep_raw = torch.is_grad_enabled() and (qkv.requires_grad or q_weight.requires_grad or k_weight.requires_grad)
-    return _QkNormRopeAttnFn.apply(qkv, q_weight, k_weight, rope_tab, int(heads), float(scale), float(eps), bool(keep_raw))
+    if head_dim == 64:
+        return _QkNormRopeAttnFn.apply(qkv, q_weight, k_weight, rope_tab, int(heads), float(scale), float(eps), bool(keep_raw))
+    ops._require(head_dim == 72, f"qk_norm_rope_attention: head_dim={head_dim} must be 64 or 72")
+    return _QkNormRopeAttnHdFn.apply(qkv, q_weight, k_weight, rope_tab, int(heads), float(scale), float(eps), bool(keep_raw), 72)
 
 
 def swiglu(u: torch.Tensor) -> torch.Tensor:
@@ -139,12 +189,12 @@ class _RmsWeight(nn.Module):
 
 
 class _LightningAttn(nn.Module):
-    def __init__(self, hidden: int, use_qknorm: bool):
+    def __init__(self, hidden: int, use_qknorm: bool, head_dim: int = 64):
         super().__init__()
         self.qkv = nn.Linear(hidden, 3 * hidden)
         if use_qknorm:
-            self.q_norm = _RmsWeight(64)
-            self.k_norm = _RmsWeight(64)
+            self.q_norm = _RmsWeight(head_dim)
+            self.k_norm = _RmsWeight(head_dim)
         self.proj = nn.Linear(hidden, hidden)
 
 
@@ -168,11 +218,11 @@ def swiglu_inner(hidden: int, mlp_ratio: float) -> int:
 
 
 class LightningDiTBlock(nn.Module):
-    def __init__(self, hidden: int, mlp_ratio: float, use_rmsnorm: bool, use_qknorm: bool, use_swiglu: bool):
+    def __init__(self, hidden: int, mlp_ratio: float, use_rmsnorm: bool, use_qknorm: bool, use_swiglu: bool, head_dim: int = 64):
         super().__init__()
         if use_rmsnorm:
             self.norm1 = _RmsWeight(hidden)
-        self.attn = _LightningAttn(hidden, use_qknorm)
+        self.attn = _LightningAttn(hidden, use_qknorm, head_dim)
         if use_rmsnorm:
             self.norm2 = _RmsWeight(hidden)
         self.mlp = _SwiGLUMlp(hidden, swiglu_inner(hidden, mlp_ratio)) if use_swiglu else _GeluMlp(hidden, int(hidden * mlp_ratio))
@@ -199,17 +249,17 @@ class LightningDiT(DiT):
     def __init__(self, input_size=16, patch_size: int = 1, in_channels: int = 32, hidden_size: int = 768, depth: int = 12,
                  num_classes: int = 1000, mlp_ratio: float = 4.0, class_dropout_prob: float = 0.1, use_rope: bool = True,
                  frequency_embedding_size: int = 256, generator: Optional[torch.Generator] = None, use_rmsnorm: bool = True,
-                 use_qknorm: bool = True, use_swiglu: bool = True):
+                 use_qknorm: bool = True, use_swiglu: bool = True, head_dim: int = 64):
         if hidden_size > 1536:
             raise ValueError(f"LightningDiT: hidden_size={hidden_size} is above 1536, the widest row of the adaLN kernels")
         super().__init__(input_size, patch_size, in_channels, hidden_size, depth, num_classes, mlp_ratio, class_dropout_prob, use_rope,
-                         frequency_embedding_size, generator)
+                         frequency_embedding_size, generator, head_dim)
         self.use_rmsnorm, self.use_qknorm, self.use_swiglu = bool(use_rmsnorm), bool(use_qknorm), bool(use_swiglu)
         self.mlp_inner = swiglu_inner(hidden_size, mlp_ratio)
         if self.use_swiglu and self.mlp_inner < 1:
             raise ValueError(f"LightningDiT: mlp_ratio={mlp_ratio} gives no SwiGLU inner width")
         self.mlp_inner_padded = _round_up(self.mlp_inner, 32)
-        self.blocks = nn.ModuleList([LightningDiTBlock(hidden_size, mlp_ratio, self.use_rmsnorm, self.use_qknorm, self.use_swiglu)
+        self.blocks = nn.ModuleList([LightningDiTBlock(hidden_size, mlp_ratio, self.use_rmsnorm, self.use_qknorm, self.use_swiglu, self.head_dim)
                                      for _ in range(depth)])
         self.final_layer = _LightningFinal(hidden_size, self.patch_cols, self.use_rmsnorm)
         self._built = True
@@ -269,9 +319,9 @@ class LightningDiT(DiT):
             a, hs = self._norm(h, blk.norm1 if rms else None, mod, 0, C, sink, True)
             qkv = ops.linear(a, blk.attn.qkv.weight, blk.attn.qkv.bias).view(B, N, 3 * C)
             if self.use_qknorm:
-                o = qk_norm_rope_attention(qkv, blk.attn.q_norm.weight, blk.attn.k_norm.weight, tab, self.num_heads, 0.125, LN_EPS)
+                o = qk_norm_rope_attention(qkv, blk.attn.q_norm.weight, blk.attn.k_norm.weight, tab, self.num_heads, self.attn_scale, LN_EPS, self.head_dim)
             else:
-                o = ops.attention(qkv, tab, self.num_heads, 0.125)
+                o = ops.attention(qkv, tab, self.num_heads, self.attn_scale, self.head_dim)
             a = ops.linear(o.view(B * N, C), blk.attn.proj.weight, blk.attn.proj.bias)
             h = gate_residual(hs, a, mod, 2 * C, N, sink)
             a, hs = self._norm(h, blk.norm2 if rms else None, mod, 3 * C, 4 * C, sink, False)
@@ -305,9 +355,14 @@ def state_dict_keys(depth: int, use_rmsnorm: bool = True, use_qknorm: bool = Tru
 
 def create_lightning_dit(name: str = "LightningDiT-B", input_size=16, patch_size: int = 1, in_channels: int = 32, num_classes: int = 1000,
                          **kwargs) -> LightningDiT:
-    """`LightningDiT-B` (768 wide, 12 deep) or `LightningDiT-L` (1024, 24).  LightningDiT-XL (1152 = 16 heads of 72) is not offered:
-    head_dim is 64 here."""
+    """`LightningDiT-B` (768 wide, 12 deep) or `LightningDiT-L` (1024, 24), both at head_dim 64.  LightningDiT-XL (1152 wide, 28 deep,
+    16 heads of 72) is `lightning_dit_xl`."""
     if name not in LIGHTNING_PRESETS:
         raise ValueError(f"create_lightning_dit: name={name!r} is not one of {sorted(LIGHTNING_PRESETS)}")
     hidden, depth = LIGHTNING_PRESETS[name]
     return LightningDiT(input_size, patch_size, in_channels, hidden, depth, num_classes, **kwargs)
+
+
+def lightning_dit_xl(input_size=16, patch_size: int = 1, in_channels: int = 32, num_classes: int = 1000, **kwargs) -> LightningDiT:
+    """LightningDiT-XL, the configuration the reference's downstream step names: 1152 wide, 28 deep, 16 heads of head_dim 72."""
+    return LightningDiT(input_size, patch_size, in_channels, 1152, 28, num_classes, head_dim=72, **kwargs)

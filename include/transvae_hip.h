@@ -680,6 +680,31 @@ int tv_qknorm_rope_bwd(const void* qkv, const float* wq, const float* wk, void* 
 int tv_swiglu_fwd(const void* u, void* h, long long T, int Hp, void* stream);
 int tv_swiglu_bwd(const void* u, const void* dh, void* du, long long T, int Hp, void* stream);
 
+/* The head_dim 72 family (csrc/attention_hd.hip; DiT-XL / LightningDiT-XL: 1152 = 16 heads of 72) --------------------------------------
+ * The entries above at another head dimension: the same argument lists plus `head_dim`, which must be 72 here (any other value
+ * returns TV_ERR_ARG with an error text naming head_dim; 64 has the entries above).  Heads sit at their natural stride, nothing in
+ * HBM is padded: qkv [B, N, 3, heads, 72] bf16 (a head vector is 144 bytes = nine 16-byte pieces), o [B, N, heads, 72] bf16, lse
+ * [B, heads, N] fp32, delta [2, B, heads, N] fp32 scratch, the table [N, 4, 36] fp32 (cos1, sin1, cos2, sin2 of 36 pairs), wq / wk
+ * / dwq / dwk fp32 [72].  Tensors 16-byte aligned; B N 3 heads < 2^31.  The pads of the MFMA shapes (72 -> 80 in q.k, -> 96 in P V)
+ * live in registers and LDS only and are zeros by construction: no load or store touches an address outside the head vector, token
+ * row or statistics row it belongs to.  No atomics; the same bits on every run.
+ * tv_attn_fwd_hd / tv_attn_bwd_hd: as tv_attn_fwd / tv_attn_bwd, any N >= 1; the policies are stated in the file header.
+ * tv_rope_qk_hd: as tv_rope_qk.
+ * tv_qknorm_rope_fwd_hd / _bwd_hd: as tv_qknorm_rope_fwd / _bwd with r = rsqrt(mean_72(q^2) + eps): a head vector is a 16-lane group,
+ * lanes 0..8 one piece each (a chain of 8 FMAs), lanes 9..15 zeros that touch no memory, a four-step xor butterfly; mean = sum times
+ * fp32(1 / 72).  dwq / dwk: per lane group its vectors in pass order, the 16 groups of a block in order, block k in lane k % 64 in
+ * order, the 64 lanes in order.  partials: tv_qknorm_rope_bwd_hd_partial_count(B, N, heads, head_dim) floats (-1: bad arguments).
+ * Rounding contract: DESIGN.md section 3.1 row Y. */
+int tv_attn_fwd_hd(const void* qkv, void* o, float* lse, int B, int N, int heads, int head_dim, float scale, void* stream);
+int tv_attn_bwd_hd(const void* qkv, const void* o, const void* d_o, const float* lse, float* delta, const float* rope_tab, void* dqkv, int B,
+                   int N, int heads, int head_dim, float scale, void* stream);
+int tv_rope_qk_hd(void* qkv, const float* tab, int B, int N, int heads, int head_dim, int transpose, void* stream);
+int tv_qknorm_rope_fwd_hd(const void* qkv, const float* wq, const float* wk, const float* rope_tab, void* out, int B, int N, int heads,
+                          int head_dim, float eps, void* stream);
+long long tv_qknorm_rope_bwd_hd_partial_count(int B, int N, int heads, int head_dim);
+int tv_qknorm_rope_bwd_hd(const void* qkv, const float* wq, const float* wk, void* dqkv, float* dwq, float* dwk, float* partials, int B, int N,
+                          int heads, int head_dim, float eps, void* stream);
+
 
 /* Generation metrics (csrc/genmetrics.hip) -------------------------------------------------------------------------------------------
  * Squared distance of the two pairwise kernels: D(a, b) = sum_c (a_c - b_c)^2 as ONE fp32 chain over c = 0 .. d - 1 in order, diff =
