@@ -1,6 +1,6 @@
 // Latent DiT: the adaLN conditioning arithmetic of its two block variants and the flow-matching edge (transvae/dit.py and
 // transvae/lightning_dit.py drive them; the token GEMMs and attention are tv_igemm_nt / tv_wgrad_tn / tv_attn_*).  DESIGN.md section 3.1
-// rows E and J hold the rounding contracts, sections 3.4 and 3.6 the protocols.  Rows are tokens: row r of a [B N, C] matrix belongs to
+// rows E and J hold the rounding contracts, sections 3.4, 3.6 and 3.7 the protocols.  Rows are tokens: row r of a [B N, C] matrix belongs to
 // sample r / N, whose modulation is row r / N of an fp32 [B, ld] matrix; shift / scale / gate are column ranges of it, given as offsets.
 //
 //   tv_adaln_fwd           y = bf16(fma(xhat, 1 + scale, shift)), xhat = (x - mean) rstd, two-pass statistics, one wave per row
@@ -13,6 +13,8 @@
 //   tv_flow_rows           patch rows of x_t = fma(t, x, (1 - t) e), x = (lat - mean) rstd   (no noise: the rows of x)
 //   tv_flow_loss           mean over the real columns of (pred - (x - e))^2 and its gradient
 //   tv_flow_euler          x += dt (v_u + s (v_c - v_u)), un-patchified on the fly
+//   tv_flow_loss_cos       tv_flow_loss plus cos_weight times the mean over the latent pixels of 1 - cos(pred, x - e), one gradient
+//   tv_flow_heun           the corrector of a Heun step: x += dt / 2 (g2 - g1), each g as in tv_flow_euler
 //
 // The per-sample sums never cross a sample inside a block: the grids of the reducing kernels are cut per sample (blockIdx.y = sample,
 // blockIdx.x = a slab of its rows), so a row count that is no multiple of the slab leaves a short last slab instead of a block that
@@ -24,6 +26,7 @@
 //   tv_adaln_fwd, tv_adaln_rms_fwd  4 T C        tv_adaln_bwd, tv_adaln_rms_bwd  6 T C (8 T C with dres)
 //   tv_gate_residual_fwd  6 T C      tv_gate_residual_bwd  6 T C
 //   tv_flow_rows  4 B D h w (8 with noise) + 2 T ld     tv_flow_loss  8 B D h w + 4 T ld     tv_flow_euler  8 B D h w + 2 T ld (4 guided)
+//   tv_flow_loss_cos  as tv_flow_loss     tv_flow_heun  8 B D h w + 2 T ld per unguided, 4 T ld per guided evaluation
 #include "row_wave.h"
 
 #include <math.h>
@@ -38,6 +41,7 @@ constexpr int AD_DW_LANES = 16;     // sample lanes of the dw sum
 constexpr int GR_RPB = 64;
 constexpr int GR_MAX_C = 2048;      // one 16-byte chunk per thread column
 constexpr int FL_MAX_BLOCKS = 1024;
+constexpr double FL_COS_EPS2 = 1e-16;   // eps^2 of the cosine term, eps = 1e-8: max(n, eps) = sqrt(max(n^2, eps^2))
 
 // xhat of one row held by a wave (row_wave.h), in place; returns rstd
 //   RMS = false  two passes: the mean, then the squared deviations from it (the scheme of tv_rownorm_fwd mode 2); xhat = (x - mean) rstd
@@ -359,6 +363,129 @@ __global__ __launch_bounds__(256) void flow_euler_kernel(float* __restrict__ x, 
     }
 }
 
+// tv_flow_loss with the per-position cosine term.  The thread layout, the grid and the fp64 order of the squared-error sum are those of
+// flow_loss_kernel, so that half of the result has the same bits.  A position is the D columns q D .. q D + D - 1 of a row; a thread
+// forms the three sums of every position that its eight columns touch (fp32 fma chains over c = 0 .. D - 1, the same bits in every
+// thread that forms them: a position that spans several vectors is summed once per vector), cos and the two reciprocal norms from them
+// in fp64 rounded once each, and the thread that holds column q D adds 1 - cos to the second sum.
+__global__ __launch_bounds__(256) void flow_loss_cos_kernel(const bf16* __restrict__ pred, const float* __restrict__ lat, const float* __restrict__ mean,
+                                                            const float* __restrict__ rstd, const float* __restrict__ noise, bf16* __restrict__ dpred,
+                                                            double* __restrict__ partials, long long total, FlowGeo g, float cmse, float ccos) {
+    __shared__ double wpart[2][4];
+    double acc = 0.0, accc = 0.0;
+    const long long hw = (long long)g.h * g.w;
+    for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+        const long long row = idx / g.ldv;
+        const int col0 = (int)(idx - row * g.ldv) * 8;
+        const bf16* __restrict__ prow = pred + row * g.ldv * 8;
+        const bf16x8 pv = *(const bf16x8*)(pred + idx * 8);
+        bf16x8 o = {0, 0, 0, 0, 0, 0, 0, 0};
+        int qcur = -1;
+        bool live = false;
+        float cosv = 0.f, rp = 0.f, rv = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int col = col0 + e;
+            if (col < g.F) {
+                const int q = col / g.D, c = col - q * g.D;
+                long long lo, no;
+                int cc;
+                if (q != qcur) {
+                    qcur = q;
+                    flow_index(g, row, q * g.D, lo, no, cc);
+                    float np2 = 0.f, nv2 = 0.f, dot = 0.f;
+                    for (cc = 0; cc < g.D; ++cc) {
+                        const float vv = (lat[lo + cc * g.sc] - mean[cc]) * rstd[cc] - noise[no + cc * hw];
+                        const float pp = (float)prow[q * g.D + cc];
+                        np2 = fmaf(pp, pp, np2);
+                        nv2 = fmaf(vv, vv, nv2);
+                        dot = fmaf(pp, vv, dot);
+                    }
+                    live = (double)np2 > FL_COS_EPS2;          // n_p <= eps: cos = 0 and no gradient from the term
+                    cosv = rp = rv = 0.f;
+                    if (live) {
+                        const double nvc = fmax((double)nv2, FL_COS_EPS2);
+                        cosv = (float)((double)dot / sqrt((double)np2 * nvc));
+                        rp = (float)(1.0 / sqrt((double)np2));
+                        rv = (float)(1.0 / sqrt(nvc));
+                    }
+                    if (c == 0) accc += 1.0 - (double)cosv;
+                }
+                flow_index(g, row, col, lo, no, cc);
+                const float v = (lat[lo] - mean[cc]) * rstd[cc] - noise[no];
+                const float pp = (float)pv[e];
+                const float d = pp - v;
+                acc += (double)d * (double)d;
+                float gr = cmse * d;
+                if (live) gr = fmaf(-ccos, (v * rv - (cosv * pp) * rp) * rp, gr);
+                o[e] = (bf16)gr;
+            }
+        }
+        if (dpred) *(bf16x8*)(dpred + idx * 8) = o;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        acc += __shfl_xor(acc, o, 64);
+        accc += __shfl_xor(accc, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        wpart[0][threadIdx.x >> 6] = acc;
+        wpart[1][threadIdx.x >> 6] = accc;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) partials[threadIdx.x * gridDim.x + blockIdx.x] = ((wpart[threadIdx.x][0] + wpart[threadIdx.x][1]) + wpart[threadIdx.x][2]) + wpart[threadIdx.x][3];
+}
+
+// partials: the nblk squared-error sums, then the nblk cosine sums; each summed as flow_loss_finalize_kernel does
+// out = {mse sum, mse mean, cos sum, cos mean, mse mean + cos_weight cos mean}
+__global__ __launch_bounds__(64) void flow_loss_cos_finalize_kernel(const double* __restrict__ partials, int nblk, double count, double count_pos,
+                                                                    double cos_weight, double* __restrict__ out) {
+    double a = 0.0, b = 0.0;
+    for (int k = threadIdx.x; k < nblk; k += 64) {
+        a += partials[k];
+        b += partials[nblk + k];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_xor(a, o, 64);
+        b += __shfl_xor(b, o, 64);
+    }
+    if (threadIdx.x == 0) {
+        out[0] = a;
+        out[1] = a / count;
+        out[2] = b;
+        out[3] = b / count_pos;
+        out[4] = out[1] + cos_weight * out[3];
+    }
+}
+
+// the corrector of a Heun step on x that holds the predictor's x + dt g1: x = fma(dt / 2, g2 - g1, x), g_k as in flow_euler_kernel
+__global__ __launch_bounds__(256) void flow_heun_kernel(float* __restrict__ x, const bf16* __restrict__ v1, const bf16* __restrict__ v2, long long total,
+                                                        long long half, FlowGeo g, float hdt, float s, int guided1, int guided2) {
+    for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+        const long long row = idx / g.ldv;
+        const int col0 = (int)(idx - row * g.ldv) * 8;
+        if (col0 >= g.F) continue;
+        const bf16x8 c1 = *(const bf16x8*)(v1 + idx * 8), c2 = *(const bf16x8*)(v2 + idx * 8);
+        bf16x8 u1 = {0, 0, 0, 0, 0, 0, 0, 0}, u2 = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (guided1) u1 = *(const bf16x8*)(v1 + half + idx * 8);
+        if (guided2) u2 = *(const bf16x8*)(v2 + half + idx * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int col = col0 + e;
+            if (col < g.F) {
+                long long lo, no;
+                int c;
+                flow_index(g, row, col, lo, no, c);
+                float g1 = (float)c1[e], g2 = (float)c2[e];
+                if (guided1) g1 = fmaf(s, g1 - (float)u1[e], (float)u1[e]);
+                if (guided2) g2 = fmaf(s, g2 - (float)u2[e], (float)u2[e]);
+                x[no] = fmaf(hdt, g2 - g1, x[no]);
+            }
+        }
+    }
+}
+
 int ad_check(const char* name, int B, int N, int C, int ld, int max_c) {
     if (B <= 0 || N <= 0 || C <= 0 || C % 8 != 0 || C > max_c || ld < C || B > 65535 || (long long)B * N >= (1ll << 31)) {
         tv_set_error("%s: bad shape B=%d N=%d C=%d ld=%d (C %% 8 == 0, C <= %d, ld >= C, B <= 65535, B N < 2^31)", name, B, N, C, ld, max_c);
@@ -550,5 +677,44 @@ extern "C" int tv_flow_euler(float* x, const void* v, int B, int D, int h, int w
     hipLaunchKernelGGL(flow_euler_kernel, dim3(flow_blocks(total, 65536)), dim3(256), 0, (hipStream_t)stream, x, (const bf16*)v, total, total * 8, g, dt,
                        cfg_scale, guided ? 1 : 0);
     TV_CHECK_LAUNCH("tv_flow_euler");
+    return TV_OK;
+}
+
+extern "C" long long tv_flow_loss_cos_partial_count(int B, int D, int h, int w, int patch, int ld) {
+    const long long n = tv_flow_loss_partial_count(B, D, h, w, patch, ld);
+    return n < 0 ? n : 2 * n;          // doubles: the squared-error partials, then the cosine partials
+}
+
+extern "C" int tv_flow_loss_cos(const void* pred, const float* lat, long long sn, long long sc, const float* mean, const float* rstd,
+                                const float* noise, void* dpred, double* out, double* partials, int B, int D, int h, int w, int patch, int ld,
+                                float cos_weight, float grad_scale, void* stream) {
+    FlowGeo g;
+    if (flow_geo("tv_flow_loss_cos", sn, sc, B, D, h, w, patch, ld, g)) return TV_ERR_ARG;
+    TV_CHECK_ARG(pred && lat && mean && rstd && noise && out && partials, "tv_flow_loss_cos: null pointer");
+    TV_CHECK_ARG((((uintptr_t)pred | (uintptr_t)dpred) & 15) == 0 && (((uintptr_t)out | (uintptr_t)partials) & 7) == 0,
+                 "tv_flow_loss_cos: pred / dpred must be 16-byte aligned, out / partials 8-byte aligned");
+    TV_CHECK_ARG(cos_weight >= 0.f && cos_weight < INFINITY, "tv_flow_loss_cos: cos_weight=%g must be finite and not negative", (double)cos_weight);
+    const long long total = (long long)B * g.N * g.ldv;
+    const double count = (double)B * g.N * g.F, count_pos = (double)B * g.h * g.w;
+    const unsigned nblk = flow_blocks(total, FL_MAX_BLOCKS);
+    hipLaunchKernelGGL(flow_loss_cos_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const bf16*)pred, lat, mean, rstd, noise, (bf16*)dpred,
+                       partials, total, g, (float)(2.0 * (double)grad_scale / count), (float)((double)grad_scale * (double)cos_weight / count_pos));
+    TV_CHECK_LAUNCH("tv_flow_loss_cos");
+    hipLaunchKernelGGL(flow_loss_cos_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)partials, (int)nblk, count, count_pos,
+                       (double)cos_weight, out);
+    TV_CHECK_LAUNCH("tv_flow_loss_cos (finalise)");
+    return TV_OK;
+}
+
+extern "C" int tv_flow_heun(float* x, const void* v1, const void* v2, int B, int D, int h, int w, int patch, int ld, float dt, float cfg_scale,
+                            int guided1, int guided2, void* stream) {
+    FlowGeo g;
+    if (flow_geo("tv_flow_heun", (long long)D * h * w, (long long)h * w, B, D, h, w, patch, ld, g)) return TV_ERR_ARG;
+    TV_CHECK_ARG(x && v1 && v2, "tv_flow_heun: null pointer");
+    TV_CHECK_ARG((((uintptr_t)v1 | (uintptr_t)v2) & 15) == 0, "tv_flow_heun: v1 / v2 must be 16-byte aligned");
+    const long long total = (long long)B * g.N * g.ldv;
+    hipLaunchKernelGGL(flow_heun_kernel, dim3(flow_blocks(total, 65536)), dim3(256), 0, (hipStream_t)stream, x, (const bf16*)v1, (const bf16*)v2, total,
+                       total * 8, g, 0.5f * dt, cfg_scale, guided1 ? 1 : 0, guided2 ? 1 : 0);
+    TV_CHECK_LAUNCH("tv_flow_heun");
     return TV_OK;
 }

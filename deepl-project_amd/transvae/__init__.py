@@ -26,7 +26,8 @@ its gradient and top-1 / top-5 counts in one pass, `LinearProbe` one linear laye
 (transvae/dit.py, csrc/dit.hip): `DiT` / `create_dit` are adaLN-Zero DiT blocks on the stored latents (token GEMMs and attention on
 the existing kernels, the conditioning arithmetic and the flow-matching edge in csrc/dit.hip); `flow_matching_loss` is one training
 step's loss and backward, `fit_dit` trains on `extract_latents` shards with `FusedAdamW`, `sample_latents` / `sample_images`
-integrate the velocity field with Euler steps and classifier-free guidance and decode through the autoencoder.  Generator evaluation
+integrate the velocity field with Euler steps and classifier-free guidance and decode through the autoencoder; the LightningDiT recipe
+is behind keywords whose defaults change nothing (`cosine_weight`; `method="heun"`, `timestep_shift`, `cfg_interval`).  Generator evaluation
 (transvae/evaluate_dit.py, transvae/metrics_gen.py, csrc/genmetrics.hip): `evaluate_dit` samples, extracts Inception features and
 returns gFID, Inception Score (`InceptionScore`) and the k-NN precision / recall (`knn_radius`, `manifold_hits`,
 `precision_recall`) against a `reference_statistics` dict; `ParamEMA` (transvae/optim.py) is the weight average they are measured on,

@@ -7,11 +7,13 @@ The reference names the stage only (`train_dit.py` / `evaluate_dit.py`, both TOD
     attention          2-D RoPE in place, flash attention, head_dim 64 or 72         `ops.attention`
     conditioning rows  adaLN (LayerNorm-hat, 1 + scale, shift), gate + residual      `adaln` / `gate_residual` (csrc/dit.hip)
     flow-matching edge x_t rows from latents, loss + gradient, Euler step            `flow_rows` / `flow_loss` / `flow_euler`
+    the recipe         loss with the cosine term, Heun corrector     `flow_loss_cos` / `flow_heun`
     conditioning path  timestep sinusoid + MLP, label embedding, SiLU, the adaLN_modulation linears: B rows, 1/N of the token
                        work, plain fp32 torch under autograd
 
 `DiT` keeps fp32 master weights under the public DiT state-dict names; `flow_matching_loss` computes the loss and runs the backward;
-`sample_latents` / `sample_images` integrate the velocity field with Euler steps and classifier-free guidance; `fit_dit` streams the
+`sample_latents` / `sample_images` integrate the velocity field with Euler or Heun steps on an optionally shifted time grid, with
+classifier-free guidance inside an interval of t; `fit_dit` streams the
 shards with `FusedAdamW`.  There is no CPU fallback: host tensors raise.
 """
 from __future__ import annotations
@@ -237,6 +239,50 @@ def flow_euler(x: torch.Tensor, v: torch.Tensor, patch_size: int, dt: float, cfg
     with torch.cuda.device(x.device):
         L.check(L.load().tv_flow_euler(ops._p(x), ops._p(v), B, D, h, w, p, ld, float(dt), float(cfg_scale or 0.0), int(guided), ops._stream()),
                 "tv_flow_euler")
+    return x
+
+
+def flow_loss_cos(pred: torch.Tensor, latents: torch.Tensor, mean: torch.Tensor, rstd: torch.Tensor, noise: torch.Tensor, patch_size: int,
+                  cos_weight: float, grad_scale: float = 1.0, want_grad: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """`flow_loss` with the per-position cosine term: (fp64 [5] = {mse sum, mse mean, sum and mean over the
+    B h w latent pixels of 1 - cos(pred, x - e), mse mean + cos_weight cos mean}, bf16 gradient of the last times `grad_scale` | None)."""
+    if not (math.isfinite(float(cos_weight)) and float(cos_weight) >= 0.0):
+        raise ValueError(f"flow_loss_cos: cos_weight={cos_weight!r} must be finite and not negative")
+    x = _latent_view(latents, "flow_loss_cos")
+    B, D, h, w = x.shape
+    p = int(patch_size)
+    ld = _round_up(p * p * D, 32)
+    ops._need_gpu(pred)
+    ops._require(pred.dtype == torch.bfloat16 and tuple(pred.shape) == (B * (h // p) * (w // p), ld) and pred.is_contiguous(),
+                 "flow_loss_cos: pred must be contiguous bf16 [B N, ld]")
+    noise = _dense(noise, x, "flow_loss_cos: noise")
+    lib = L.load()
+    with torch.cuda.device(x.device):
+        out = torch.empty(5, dtype=torch.float64, device=x.device)
+        part = torch.empty(lib.tv_flow_loss_cos_partial_count(B, D, h, w, p, ld), dtype=torch.float64, device=x.device)
+        dpred = torch.empty_like(pred) if want_grad else None
+        L.check(lib.tv_flow_loss_cos(ops._p(pred), ops._p(x), x.stride(0), x.stride(1), ops._p(mean), ops._p(rstd), ops._p(noise), ops._p(dpred),
+                                     ops._p(out), ops._p(part), B, D, h, w, p, ld, float(cos_weight), float(grad_scale), ops._stream()),
+                "tv_flow_loss_cos")
+    return out, dpred
+
+
+def flow_heun(x: torch.Tensor, v1: torch.Tensor, v2: torch.Tensor, patch_size: int, dt: float, cfg_scale: float = 1.0, guided1: bool = False,
+              guided2: bool = False) -> torch.Tensor:
+    """The corrector of a Heun step, in place on dense fp32 x [B, D, h, w] that holds the predictor's x + dt g1: x += dt / 2 (g2 - g1).
+    g_k is read from bf16 rows v_k [B N, ld]; with `guided_k`, v_k has 2 B N rows (conditional half first) and
+    g_k = v_u + cfg_scale (v_c - v_u), as in `flow_euler`."""
+    ops._need_gpu(x, v1, v2)
+    ops._require(x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous(), "flow_heun: dense fp32 x [B, D, h, w]")
+    B, D, h, w = x.shape
+    p = int(patch_size)
+    ld = _round_up(p * p * D, 32)
+    for v, guided, what in ((v1, guided1, "v1"), (v2, guided2, "v2")):
+        ops._require(v.dtype == torch.bfloat16 and v.is_contiguous() and v.device == x.device and
+                     tuple(v.shape) == ((2 if guided else 1) * B * (h // p) * (w // p), ld), f"flow_heun: {what} must be contiguous bf16 [(2) B N, ld]")
+    with torch.cuda.device(x.device):
+        L.check(L.load().tv_flow_heun(ops._p(x), ops._p(v1), ops._p(v2), B, D, h, w, p, ld, float(dt), float(cfg_scale), int(bool(guided1)),
+                                      int(bool(guided2)), ops._stream()), "tv_flow_heun")
     return x
 
 
@@ -503,17 +549,25 @@ def draw_t(B: int, t_sampling: str, generator: Optional[torch.Generator], device
     raise ValueError(f"t_sampling={t_sampling!r} must be 'uniform' or 'lognorm'")
 
 
+def _check_cosine_weight(cosine_weight: float):
+    if not (math.isfinite(float(cosine_weight)) and float(cosine_weight) >= 0.0):
+        raise ValueError(f"cosine_weight={cosine_weight!r} must be finite and not negative")
+
+
 def flow_matching_loss(dit: DiT, latents: torch.Tensor, labels: torch.Tensor, stats: Stats, *, t: Optional[torch.Tensor] = None,
                        noise: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None, t_sampling: str = "lognorm",
-                       grad_scale: float = 1.0, check_labels: bool = True) -> torch.Tensor:
+                       grad_scale: float = 1.0, check_labels: bool = True, cosine_weight: float = 0.0) -> torch.Tensor:
     """One flow-matching step's loss, and its backward when gradients are enabled.
 
     x = (latents - mean) / std with `stats`, e = `noise` or N(0, I), t = `t` or drawn by `t_sampling`; the model sees the rows of
     t x + (1 - t) e and the loss is the mean of (v_pred - (x - e))^2 over the real columns.  In training mode each label is
     replaced by the null class with `dit.class_dropout_prob`.  Everything random is drawn with `generator` on the latents' device.
+    With `cosine_weight` > 0 the loss is that mean plus `cosine_weight` times the mean over the latent pixels of
+    1 - cos(v_pred, x - e) across the channels (`flow_loss_cos`); at 0.0 the term does not exist.
     Returns the loss as an fp64 device scalar (no synchronisation); the parameters' `.grad` hold `grad_scale` times its gradient."""
     if t_sampling not in ("uniform", "lognorm"):
         raise ValueError(f"t_sampling={t_sampling!r} must be 'uniform' or 'lognorm'")
+    _check_cosine_weight(cosine_weight)
     latents = _take_mu(dit, latents)
     if check_labels:
         dit.check_labels(labels)
@@ -535,20 +589,58 @@ def flow_matching_loss(dit: DiT, latents: torch.Tensor, labels: torch.Tensor, st
         rows = flow_rows(latents, mean, rstd, dit.patch_size, noise, t)
         train = torch.is_grad_enabled()
         pred = dit(rows, t, y)
-        out, dpred = flow_loss(pred.detach(), latents, mean, rstd, noise, dit.patch_size, grad_scale, train)
+        if float(cosine_weight) > 0.0:
+            out, dpred = flow_loss_cos(pred.detach(), latents, mean, rstd, noise, dit.patch_size, cosine_weight, grad_scale, train)
+        else:
+            out, dpred = flow_loss(pred.detach(), latents, mean, rstd, noise, dit.patch_size, grad_scale, train)
         if train:
             pred.backward(dpred)
-    return out[1]
+    return out[4] if float(cosine_weight) > 0.0 else out[1]
+
+
+SAMPLE_METHODS = ("euler", "heun")
+
+
+def time_grid(steps: int, timestep_shift: float = 1.0) -> list:
+    """The `steps + 1` times of the sampler, t = 0 (noise) to t = 1, as Python floats (float64): u_i = i / steps and
+    t_i = s u_i / (1 + (s - 1) u_i); s < 1 spends more steps near the noise, s = 1 is the equal grid i (1 / steps) that ends at 1.0."""
+    steps, s = int(steps), float(timestep_shift)
+    if steps < 1:
+        raise ValueError(f"sample_latents: steps={steps} must be positive")
+    if not (math.isfinite(s) and s > 0.0):
+        raise ValueError(f"sample_latents: timestep_shift={timestep_shift!r} must be positive")
+    if s == 1.0:
+        dt = 1.0 / steps
+        return [i * dt for i in range(steps)] + [1.0]
+    grid = [s * (i / steps) / (1.0 + (s - 1.0) * (i / steps)) for i in range(steps)]
+    return grid + [1.0]
+
+
+def _check_sampler(method: str, timestep_shift: float, cfg_interval) -> Tuple[float, float]:
+    if method not in SAMPLE_METHODS:
+        raise ValueError(f"sample_latents: method={method!r} must be one of {SAMPLE_METHODS}")
+    if not (math.isfinite(float(timestep_shift)) and float(timestep_shift) > 0.0):
+        raise ValueError(f"sample_latents: timestep_shift={timestep_shift!r} must be positive")
+    if not (isinstance(cfg_interval, (tuple, list)) and len(cfg_interval) == 2):
+        raise ValueError(f"sample_latents: cfg_interval={cfg_interval!r} must be a (lo, hi) pair")
+    lo, hi = float(cfg_interval[0]), float(cfg_interval[1])
+    if not 0.0 <= lo <= hi <= 1.0:
+        raise ValueError(f"sample_latents: cfg_interval={cfg_interval!r} must satisfy 0 <= lo <= hi <= 1")
+    return lo, hi
 
 
 @torch.no_grad()
 def sample_latents(dit: DiT, labels: torch.Tensor, *, steps: int, cfg_scale: float = 1.0, generator: Optional[torch.Generator] = None,
-                   stats: Stats, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Euler integration of the velocity field from t = 0 (noise) to t = 1 in `steps` equal steps, then de-normalisation with
-    `stats`: fp32 latents [B, D, h, w] for `vae.decode`.  cfg_scale != 1 runs each step as one batch of 2B (labels, then the null
-    class) and steps along v_null + cfg_scale (v_label - v_null)."""
+                   stats: Stats, noise: Optional[torch.Tensor] = None, method: str = "euler", timestep_shift: float = 1.0,
+                   cfg_interval: Tuple[float, float] = (0.0, 1.0)) -> torch.Tensor:
+    """Integration of the velocity field from t = 0 (noise) to t = 1 in `steps` steps on `time_grid(steps, timestep_shift)`, then
+    de-normalisation with `stats`: fp32 latents [B, D, h, w] for `vae.decode`.  An evaluation at time t is guided iff cfg_scale != 1
+    and cfg_interval[0] <= t <= cfg_interval[1]: it runs as one batch of 2B (labels, then the null class) and gives
+    v_null + cfg_scale (v_label - v_null); an unguided one runs the B labelled rows alone.  method="euler": one evaluation per step;
+    "heun": the Euler predictor, a second evaluation at the step's end on its result, and `flow_heun`."""
     if int(steps) < 1:
         raise ValueError(f"sample_latents: steps={steps} must be positive")
+    lo, hi = _check_sampler(method, timestep_shift, cfg_interval)
     dit.check_labels(labels)
     _check_stats(stats, dit.in_channels)
     ops._need_gpu(labels)
@@ -567,13 +659,26 @@ def sample_latents(dit: DiT, labels: torch.Tensor, *, steps: int, cfg_scale: flo
         T = B * dit.tokens
         rows = torch.empty(((2 if guided else 1) * T, dit.ld), dtype=torch.bfloat16, device=dev)
         y = torch.cat([labels, torch.full_like(labels, dit.num_classes)]) if guided else labels
-        dt = 1.0 / int(steps)
-        for i in range(int(steps)):
+        grid = time_grid(steps, timestep_shift)
+
+        def velocity(tv: float):
+            """(bf16 velocity rows of the model at x and time tv, whether they hold the null-class half)"""
+            g = guided and lo <= tv <= hi
             flow_rows(x, zero, one, p, out=rows[:T])
-            if guided:
+            if g:
                 flow_rows(x, zero, one, p, out=rows[T:])
-            t = torch.full((y.shape[0],), i * dt, dtype=torch.float32, device=dev)
-            flow_euler(x, dit(rows, t, y), p, dt, float(cfg_scale) if guided else None)
+            n = (2 if g else 1) * B
+            t = torch.full((n,), tv, dtype=torch.float32, device=dev)
+            return dit(rows[:n * dit.tokens], t, y[:n]), g
+
+        equal_dt = 1.0 / int(steps) if float(timestep_shift) == 1.0 else None
+        for i in range(int(steps)):
+            dt = equal_dt if equal_dt is not None else grid[i + 1] - grid[i]
+            v1, g1 = velocity(grid[i])
+            flow_euler(x, v1, p, dt, float(cfg_scale) if g1 else None)
+            if method == "heun":
+                v2, g2 = velocity(grid[i + 1])
+                flow_heun(x, v1, v2, p, dt, float(cfg_scale), g1, g2)
         x = x * std.view(1, D, 1, 1) + mean.view(1, D, 1, 1)
     dit.train(was_training)
     return x
@@ -582,10 +687,12 @@ def sample_latents(dit: DiT, labels: torch.Tensor, *, steps: int, cfg_scale: flo
 @torch.no_grad()
 def sample_images(vae: nn.Module, dit: DiT, labels: torch.Tensor, *, steps: int, cfg_scale: float = 1.0,
                   generator: Optional[torch.Generator] = None, stats: Stats, noise: Optional[torch.Tensor] = None, grid: bool = False,
-                  nrow: int = 8) -> torch.Tensor:
+                  nrow: int = 8, method: str = "euler", timestep_shift: float = 1.0,
+                  cfg_interval: Tuple[float, float] = (0.0, 1.0)) -> torch.Tensor:
     """`sample_latents`, then `vae.decode`: the decoder's raw output [B, 3, H, W]; grid=True: the uint8 sheet of
     `to_uint8_grid(..., transform="sigmoid")`."""
-    lat = sample_latents(dit, labels, steps=steps, cfg_scale=cfg_scale, generator=generator, stats=stats, noise=noise)
+    lat = sample_latents(dit, labels, steps=steps, cfg_scale=cfg_scale, generator=generator, stats=stats, noise=noise, method=method,
+                         timestep_shift=timestep_shift, cfg_interval=cfg_interval)
     img = vae.decode(lat)
     if grid:
         from .image_io import to_uint8_grid
@@ -594,7 +701,8 @@ def sample_images(vae: nn.Module, dit: DiT, labels: torch.Tensor, *, steps: int,
 
 
 def fit_dit(train_dir, dit: DiT, *, epochs: int, batch_size: int, lr: float, weight_decay: float = 0.0, t_sampling: str = "lognorm",
-            use_flip: bool = True, seed: int = 0, log_every: int = 50, device="cuda", ema_decay: Optional[float] = None) -> Dict:
+            use_flip: bool = True, seed: int = 0, log_every: int = 50, device="cuda", ema_decay: Optional[float] = None,
+            cosine_weight: float = 0.0) -> Dict:
     """Train `dit` by flow matching on an `extract_latents` directory (or a `(latents, labels)` pair with `stats` as a third item).
 
     Shards stream one at a time in an order drawn per epoch from a host generator seeded with `seed + 1`, with a permutation inside
@@ -602,12 +710,13 @@ def fit_dit(train_dir, dit: DiT, *, epochs: int, batch_size: int, lr: float, wei
     the same generator.  t, the noise and the label dropout come from a device generator seeded with `seed`.  `FusedAdamW`,
     constant learning rate; the loss is read back once per `log_every` steps (one host synchronisation each).
     With `ema_decay` a `ParamEMA` of the weights (equal to them at the start) is updated after every optimizer step and returned
-    under "ema"; with None nothing is kept and there is no such key.
+    under "ema"; with None nothing is kept and there is no such key.  `cosine_weight` is `flow_matching_loss`'s.
     Returns {"loss" (mean of the last logging interval), "history" [{"step", "loss"}], "shard_orders", "steps", "optimizer"}."""
     if ema_decay is not None and not 0.0 <= float(ema_decay) <= 1.0:
         raise ValueError(f"fit_dit: ema_decay={ema_decay!r} must be in [0, 1] or None")
     if epochs < 1 or batch_size < 1 or not lr > 0 or log_every < 1:
         raise ValueError("fit_dit: epochs, batch_size, lr and log_every must be positive")
+    _check_cosine_weight(cosine_weight)
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("transvae.hip: this op only runs on a HIP device (MI355X); there is no CPU fallback")
@@ -646,7 +755,8 @@ def fit_dit(train_dir, dit: DiT, *, epochs: int, batch_size: int, lr: float, wei
                     if flip is not None:
                         x = torch.where(mirrored[perm[i:i + batch_size]].to(device).view(-1, 1, 1, 1), flip[idx], x)
                     opt.zero_grad(set_to_none=True)
-                    acc += flow_matching_loss(dit, x, lab[idx], stats, generator=dev_gen, t_sampling=t_sampling, check_labels=False)
+                    acc += flow_matching_loss(dit, x, lab[idx], stats, generator=dev_gen, t_sampling=t_sampling, check_labels=False,
+                                              cosine_weight=cosine_weight)
                     opt.step()
                     if ema is not None:
                         ema.update()

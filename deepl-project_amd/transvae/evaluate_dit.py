@@ -32,11 +32,13 @@ def _load_reference(reference) -> Dict:
 def evaluate_dit(vae, dit: DiT, reference: Union[Dict, str], *, fid_net, num_samples: int = 10000, batch_size: int = 128, steps: int = 50,
                  cfg_scale: float = 1.0, metrics: Sequence[str] = METRICS, is_head: Optional[InceptionScore] = None, k: int = 3,
                  seed: int = 0, labels: Optional[torch.Tensor] = None, ema=None, transform: str = "clip", max_features: int = 10000,
-                 return_features: bool = False, stats=None) -> Dict:
+                 return_features: bool = False, stats=None, method: str = "euler", timestep_shift: float = 1.0,
+                 cfg_interval=(0.0, 1.0)) -> Dict:
     """{"gfid", "is", "precision", "recall", "n"} (restricted to `metrics`) of `num_samples` images sampled from `dit`.
 
     Sample i has label i % dit.num_classes unless `labels` [num_samples] is given; the noise comes batch by batch from a device
-    generator seeded with `seed`; sampling is `sample_images(vae, dit, ..., steps, cfg_scale)` with the model in eval mode, under
+    generator seeded with `seed`; sampling is `sample_images(vae, dit, ..., steps, cfg_scale)` (with `method`, `timestep_shift` and
+    `cfg_interval` handed to `sample_latents`, which validates them before the first launch) with the model in eval mode, under
     `ema.applied(dit)` when a `ParamEMA` is handed in.  `stats` is the `latents_stats.pt` dict (or a (mean, std) pair) that
     de-normalises the sampled latents; None: mean 0, std 1.  transform="clip" feeds the decoder's output to
     `fid_net.features(img, clip=True)` as `evaluate` does for rFID; "sigmoid" applies a sigmoid first, as generate.py does.
@@ -92,7 +94,8 @@ def evaluate_dit(vae, dit: DiT, reference: Union[Dict, str], *, fid_net, num_sam
         if is_head is not None and "is" in metrics:
             is_head.reset()
         for i0 in range(0, num_samples, batch_size):
-            img = sample_images(vae, dit, labels[i0:i0 + batch_size], steps=int(steps), cfg_scale=float(cfg_scale), generator=gen, stats=stats)
+            img = sample_images(vae, dit, labels[i0:i0 + batch_size], steps=int(steps), cfg_scale=float(cfg_scale), generator=gen, stats=stats,
+                                method=method, timestep_shift=timestep_shift, cfg_interval=cfg_interval)
             img = img.float()
             if transform == "sigmoid":
                 img = torch.sigmoid(img)

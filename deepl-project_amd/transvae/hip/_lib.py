@@ -146,6 +146,9 @@ SIGNATURES = {
     "tv_flow_loss_partial_count": (_LL, [_I, _I, _I, _I, _I, _I]),
     "tv_flow_loss": (_I, [_P, _P, _LL, _LL, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "tv_flow_euler": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _I, _P]),
+    "tv_flow_loss_cos_partial_count": (_LL, [_I, _I, _I, _I, _I, _I]),
+    "tv_flow_loss_cos": (_I, [_P, _P, _LL, _LL, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P]),
+    "tv_flow_heun": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _I, _I, _P]),
     "tv_adaln_rms_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _F, _P]),
     "tv_adaln_rms_bwd_partial_count": (_LL, [_I, _I, _I]),
     "tv_adaln_rms_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),

@@ -641,6 +641,23 @@ long long tv_flow_loss_partial_count(int B, int D, int h, int w, int patch, int 
 int tv_flow_loss(const void* pred, const float* lat, long long sn, long long sc, const float* mean, const float* rstd, const float* noise,
                  void* dpred, double* out, double* partials, int B, int D, int h, int w, int patch, int ld, float grad_scale, void* stream);
 int tv_flow_euler(float* x, const void* v, int B, int D, int h, int w, int patch, int ld, float dt, float cfg_scale, int guided, void* stream);
+/* tv_flow_loss_cos: tv_flow_loss with a cosine term per position (latent pixel): the D columns q D .. q D + D - 1 of a row, q < p p, any
+ * D.  With v = x - e as above and the fp32 fma chains np2 = sum p^2, nv2 = sum v^2, dot = sum p v over c = 0 .. D - 1, eps = 1e-8:
+ * cos = fp32(dot / sqrt(np2 max(nv2, eps^2))), formed in fp64 and rounded once; np2 <= eps^2: cos = 0 and the term gives no gradient
+ * (unlike autograd through cosine_similarity, which returns v / (|v| eps) for a zero prediction).  out = 5 doubles {sum d^2, its
+ * mean (the bits of tv_flow_loss), sum (1 - cos), its mean over the B h w positions, mse mean + cos_weight cos mean}, every sum
+ * in the order of tv_flow_loss.  dpred (bf16 or NULL) = bf16(fma(-fp32(grad_scale cos_weight / (B h w)), gc, fp32(2 grad_scale /
+ * count) d)), gc = (v rv - (cos p) rp) rp with rp = fp32(1 / sqrt(np2)), rv = fp32(1 / sqrt(max(nv2, eps^2))): formed in fp32, rounded
+ * once, pad columns exactly 0.  cos_weight >= 0.  partials: tv_flow_loss_cos_partial_count(...) doubles of scratch.
+ * tv_flow_heun: x holds the predictor's result x + dt g1; x = fma(dt / 2, g2 - g1, x).  g_k is read from v_k (bf16 rows, B N of them, or
+ * 2 B N with guided_k != 0) as tv_flow_euler reads its velocity: fma(cfg_scale, v_c - v_u, v_u) if guided_k, the conditional rows
+ * otherwise.  The two flags are independent.  Rounding contract: DESIGN.md section 3.1 row E (its last line); protocol: section 3.7. */
+long long tv_flow_loss_cos_partial_count(int B, int D, int h, int w, int patch, int ld);
+int tv_flow_loss_cos(const void* pred, const float* lat, long long sn, long long sc, const float* mean, const float* rstd, const float* noise,
+                     void* dpred, double* out, double* partials, int B, int D, int h, int w, int patch, int ld, float cos_weight, float grad_scale,
+                     void* stream);
+int tv_flow_heun(float* x, const void* v1, const void* v2, int B, int D, int h, int w, int patch, int ld, float dt, float cfg_scale, int guided1,
+                 int guided2, void* stream);
 
 /* LightningDiT block variants: RMSNorm adaLN, per-head qk-norm with RoPE, SwiGLU (csrc/lightning.hip) -----------------------------------
  * The conventions of the DiT block above: bf16 token matrices [B N, C], 16-byte aligned, C % 8 == 0; the fp32 [B, ld] modulation
