@@ -450,6 +450,13 @@ template <int TG, int TX, int NWM, int NWN, int RING, int VAR, int SEG, int TAPS
 int kx3_launch_v(const Kx3Args& a, dim3 grid, hipStream_t s) {
     constexpr int BYTES = RING * (TAPS == 1 ? 64 * (TG + TX) * 2 : kx_stage_bytes(TG, TX, SEG));
     static_assert(BYTES <= 160 * 1024, "LDS");
+    if (g_wgrad_pick) {   // tv_wgrad_tn_which (wgrad_tn.hip): this is the instantiation the call would launch
+        TvWgradPick& k = *g_wgrad_pick;
+        k.family = 2; k.tg = TG; k.tx = TX; k.det = DET ? 1 : 0;
+        k.seg = SEG; k.ring = RING; k.var = VAR; k.taps = TAPS;
+        k.ny = a.ny; k.chunk_px = a.chunk_px; k.plain = a.plain; k.xcd_order = a.xcd_order;
+        return 100 + a.plain;   // (the plan-only answer of kx3_launch_r)
+    }
     static TvPerDeviceOnce attr_once;
     if (attr_once.first()) {
         (void)hipFuncSetAttribute((const void*)wgrad_kx3_kernel<TG, TX, NWM, NWN, RING, VAR, SEG, TAPS, DET>, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES);
@@ -499,9 +506,10 @@ int kx3_launch_r(Kx3Args a, hipStream_t s, bool plan_only, TvDetCtx* det) {
         det->dw_elems = (long long)a.c_out * (TAPS * TAPS) * a.c_in;
         det->c_out = a.c_out;
         det->need = tv_det_need(ny, det->dw_elems, a.c_out);
+        const bool which = plan_only && g_wgrad_pick;
+        if (!plan_only || which) a.det = (ny > 1 || a.dbias || (which && g_wgrad_pick->has_bias)) ? 1 : 0;
         if (!plan_only) {
             if (det->need > det->ws_bytes || (ny > 1 && !det->ws)) return -2;
-            a.det = (ny > 1 || a.dbias) ? 1 : 0;
             if (ny > 1) {
                 a.dw = det->ws;
                 a.dw_slice = det->dw_elems;
@@ -510,7 +518,7 @@ int kx3_launch_r(Kx3Args a, hipStream_t s, bool plan_only, TvDetCtx* det) {
             }
         }
     }
-    if (plan_only) return 100 + a.plain;
+    if (plan_only && !g_wgrad_pick) return 100 + a.plain;
     a.base = (int)base;
     a.ny = ny;
     a.xcd_order = (ny > 1 && xcd) ? 1 : 0;

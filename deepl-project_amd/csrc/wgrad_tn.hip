@@ -512,6 +512,13 @@ int launch_st(const WgradArgs& a, dim3 grid, hipStream_t s) {
     if constexpr (BYTES > 160 * 1024 || (TX / NWN) % 16 != 0 || (STAGES == 3 && (!uniform || NWN != 4 || !wgrad_pipe<TG, TX, NWN>()))) {
         return -1;
     } else {
+        if (g_wgrad_pick) {   // tv_wgrad_tn_which: this is the instantiation the call would launch
+            TvWgradPick& k = *g_wgrad_pick;
+            k.family = 1; k.tg = TG; k.tx = TX; k.det = DET ? 1 : 0;
+            k.bkp = BKP; k.waves = NW; k.fast = FAST ? 1 : 0; k.stages = STAGES;
+            k.ny = a.ny; k.chunk_px = a.chunk_px; k.plain = a.plain; k.xcd_order = a.xcd_order;
+            return 0;
+        }
         static TvPerDeviceOnce attr_once;
         if (attr_once.first()) {
             (void)hipFuncSetAttribute((const void*)wgrad_tn_kernel<TG, TX, BKP, NWN, FAST, STAGES, DET>, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES);
@@ -590,9 +597,10 @@ int launch(const WgradArgs& a0, hipStream_t s, bool plan_only, double* t_model =
         det->dw_elems = (long long)a.c_out * a.kh * a.kw * a.c_in;
         det->c_out = a.c_out;
         det->need = tv_det_need(ny, det->dw_elems, a.c_out);
+        const bool which = plan_only && g_wgrad_pick && !t_model;
+        if (!plan_only || which) a.det = (ny > 1 || a.dbias || (which && g_wgrad_pick->has_bias)) ? 1 : 0;    // (one chunk, no bias: the default instantiation's plain store is already it)
         if (!plan_only) {
             if (det->need > det->ws_bytes || (ny > 1 && !det->ws)) return -2;    // (never launch into a workspace that is too small)
-            a.det = (ny > 1 || a.dbias) ? 1 : 0;    // (one chunk, no bias: the default instantiation's plain store is already it)
             if (ny > 1) {
                 a.dw = det->ws;
                 a.dw_slice = det->dw_elems;
@@ -601,7 +609,7 @@ int launch(const WgradArgs& a0, hipStream_t s, bool plan_only, double* t_model =
             }
         }
     }
-    if (plan_only) return 100 + a.plain;   // (distinct from the TV_ERR_* codes)
+    if (plan_only && !(g_wgrad_pick && !t_model)) return 100 + a.plain;   // (distinct from the TV_ERR_* codes)
     a.base = (int)base;
     a.ny = ny;
     a.xcd_order = (ny > 1 && xcd) ? 1 : 0;
@@ -620,12 +628,16 @@ int launch(const WgradArgs& a0, hipStream_t s, bool plan_only, double* t_model =
         a.x_bytes = (same && xbytes + shift < (1ll << 31) && gbytes < (1ll << 31)) ? (unsigned)xbytes : 0u;
     }
     // (w8: 8 waves, 2 per SIMD, for the 192-wide co tile: one wave's transposed-read phase overlaps the other's MFMAs)
-    if (bkp == 64) {
-        if (w8 && launch_s<TG, TX, 64, 4>(a, grid, s) == 0) return 0;
-        if (launch_s<TG, TX, 64, 2>(a, grid, s) == 0) return 0;
-    }
-    if (w8 && launch_s<TG, TX, 32, 4>(a, grid, s) == 0) return 0;
-    return launch_s<TG, TX, 32, 2>(a, grid, s);
+    auto pick = [&]() -> int {
+        if (bkp == 64) {
+            if (w8 && launch_s<TG, TX, 64, 4>(a, grid, s) == 0) return 0;
+            if (launch_s<TG, TX, 64, 2>(a, grid, s) == 0) return 0;
+        }
+        if (w8 && launch_s<TG, TX, 32, 4>(a, grid, s) == 0) return 0;
+        return launch_s<TG, TX, 32, 2>(a, grid, s);
+    };
+    const int r = pick();
+    return (plan_only && r == 0) ? 100 + a.plain : r;   // (plan_only down here: tv_wgrad_tn_which, launch_st recorded instead of launching)
 }
 
 }  // namespace
@@ -735,6 +747,34 @@ extern "C" int tv_wgrad_tn_acc(const tv_conv_desc* d, const void* x, const void*
 extern "C" int tv_wgrad_tn_overwrites(const tv_conv_desc* d) {
     const int r = wgrad_impl(d, nullptr, nullptr, nullptr, nullptr, nullptr, true);
     return r >= 100 ? r - 100 : -1;
+}
+
+// Debug hook beside tv_set_wgrad_config / tv_set_wgrad_kx3 (not in the header): which kernel tv_wgrad_tn (accum 0) / tv_wgrad_tn_acc
+// (accum 1) / tv_wgrad_tn_det (deterministic 1) would launch for this descriptor under the current hook settings, with a dbias
+// (has_bias 1) or without.  Host arithmetic only, like tv_wgrad_tn_plan: the plan-only walk of wgrad_impl, carried on to the launch
+// site, which records its template arguments (TvWgradPick, det.h).  Writes one line, e.g.
+//     "tn<192,128> bkp=64 waves=8 fast=1 stages=2 det=0 ny=2 chunk_px=1024 plain=0 xcd_order=0"
+//     "kx3<192,96> seg=64 ring=4 var=4 taps=3 det=1 ny=8 chunk_px=2048 plain=0 xcd_order=1"
+TvWgradPick* g_wgrad_pick = nullptr;
+extern "C" int tv_wgrad_tn_which(const tv_conv_desc* d, int accum, int deterministic, int has_bias, char* out, int out_bytes) {
+    TV_CHECK_ARG(out && out_bytes > 0, "tv_wgrad_tn_which: null pointer");
+    TvWgradPick k;
+    k.has_bias = has_bias ? 1 : 0;
+    TvDetCtx det;
+    g_wgrad_pick = &k;
+    const int r = wgrad_impl(d, nullptr, nullptr, nullptr, nullptr, nullptr, true, accum, deterministic ? &det : nullptr);
+    g_wgrad_pick = nullptr;
+    if (r < 100) return r < 0 ? TV_ERR_ARG : r;
+    if (!k.family) { tv_set_error("tv_wgrad_tn_which: no kernel for this configuration"); return TV_ERR_ARG; }
+    int n;
+    if (k.family == 1)
+        n = snprintf(out, (size_t)out_bytes, "tn<%d,%d> bkp=%d waves=%d fast=%d stages=%d det=%d ny=%d chunk_px=%d plain=%d xcd_order=%d", k.tg, k.tx,
+                     k.bkp, k.waves, k.fast, k.stages, k.det, k.ny, k.chunk_px, k.plain, k.xcd_order);
+    else
+        n = snprintf(out, (size_t)out_bytes, "kx3<%d,%d> seg=%d ring=%d var=%d taps=%d det=%d ny=%d chunk_px=%d plain=%d xcd_order=%d", k.tg, k.tx,
+                     k.seg, k.ring, k.var, k.taps, k.det, k.ny, k.chunk_px, k.plain, k.xcd_order);
+    TV_CHECK_ARG(n > 0 && n < out_bytes, "tv_wgrad_tn_which: buffer of %d bytes is too small", out_bytes);
+    return TV_OK;
 }
 
 // ---- deterministic form ---------------------------------------------------------------------------------

@@ -253,7 +253,9 @@ def load():
         lib.tv_set_wgrad_config.argtypes = [_I, _I, _I]
         lib.tv_set_wgrad_kx3.restype = _I
         lib.tv_set_wgrad_kx3.argtypes = [_I, _I, _I]
-        if os.environ.get("TV_WGRAD_KX3") is not None:     # A/B hook: 0 = every weight gradient through the single-tap kernel, 1 = kx3 for 3x3 only
+        lib.tv_wgrad_tn_which.restype = _I            # debug query (ops.wgrad_which): the kernel a weight-gradient call would launch
+        lib.tv_wgrad_tn_which.argtypes = [_DP, _I, _I, _I, C.c_char_p, _I]
+        if os.environ.get("TV_WGRAD_KX3") is not None:    # A/B hook: 0 = every weight gradient through the single-tap kernel, 1 = kx3 for 3x3 only
             lib.tv_set_wgrad_kx3(int(os.environ["TV_WGRAD_KX3"]), 0, 0)
         _lib = lib
     return _lib

@@ -360,6 +360,22 @@ def wgrad_det_plan(desc: L.ConvDesc, accum: bool = False):
     return ny.value, nbytes.value
 
 
+def wgrad_which(desc: L.ConvDesc, accum: bool = False, deterministic: Optional[bool] = None, has_bias: bool = True) -> dict:
+    """The kernel wgrad / wgrad_acc would launch for this descriptor now, under the current tuning hooks (tv_wgrad_tn_which: the
+    plan-only walk of the dispatch, host arithmetic, no GPU).  deterministic: None = the current mode.  Keys: 'kernel' -- the
+    instantiation, e.g. 'tn<192,128> bkp=64 waves=8 fast=1 stages=2 det=0' or 'kx3<192,96> seg=64 ring=4 var=4 taps=3 det=0' --
+    and the launch's 'ny', 'chunk_px', 'plain', 'xcd_order' as integers, besides every field of the line by its own name."""
+    det = _deterministic if deterministic is None else deterministic
+    buf = C.create_string_buffer(256)
+    L.check(L.load().tv_wgrad_tn_which(C.byref(desc), int(accum), int(det), int(has_bias), buf, len(buf)), "tv_wgrad_tn_which")
+    words = buf.value.decode().split()
+    out = {k: int(v) for k, v in (wd.split("=") for wd in words[1:])}
+    out["family"] = words[0].split("<")[0]
+    out["tile"] = words[0]
+    out["kernel"] = " ".join(wd for wd in words if wd.split("=")[0] not in ("ny", "chunk_px", "plain", "xcd_order"))
+    return out
+
+
 def _wgrad_det(desc: L.ConvDesc, x, gy, dw, dbias, acc: bool):
     lib = L.load()
     B = desc.batch

@@ -13,6 +13,7 @@ import torch
 
 from test_error_budget_host import (BF, EPS_LN, EPS_RMS, F64, ROWNORM_C_DW, WGRAD_C, check_fp32, gn_inputs, r16, rms_ln_inputs,
                                     rownorm_bwd64)
+from wgrad_matrix_cases import wgrad_ref64       # (the descriptor's own gather in fp64; shared with test_wgrad_matrix_gpu.py)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -103,27 +104,6 @@ def test_reduce_slices_rejects_bad_arguments():
 # ---------------------------------------------------------------------------------------------------------------------------
 # 2. / 3. weight gradient
 # ---------------------------------------------------------------------------------------------------------------------------
-def wgrad_ref64(x, gy, kh, kw, stride, pad, up):
-    """fp64 dw[co][ky][kx][ci] = sum_p gy[p][co] x_gathered[p][ky][kx][ci] of the descriptor's gather (nearest x2 upsampling, zero
-    padding, stride) and the same sum of absolute values; x [B, H, W, Ci], gy [B, Ho, Wo, Co] -> ([Co, kh, kw, Ci], same)"""
-    B, Ho, Wo, Co = gy.shape
-
-    def one(xx, gg):
-        xu = xx.repeat_interleave(2, 1).repeat_interleave(2, 2) if up else xx
-        hn, wn = (Ho - 1) * stride + kh, (Wo - 1) * stride + kw
-        xp = torch.zeros(B, max(hn, xu.shape[1] + 2 * pad), max(wn, xu.shape[2] + 2 * pad), xx.shape[-1], dtype=F64)
-        xp[:, pad:pad + xu.shape[1], pad:pad + xu.shape[2]] = xu
-        g2 = gg.reshape(-1, Co)
-        dw = torch.empty(Co, kh, kw, xx.shape[-1], dtype=F64)
-        for ky in range(kh):
-            for kx in range(kw):
-                xs = xp[:, ky:ky + (Ho - 1) * stride + 1:stride, kx:kx + (Wo - 1) * stride + 1:stride]
-                dw[:, ky, kx] = g2.t() @ xs.reshape(-1, xx.shape[-1])
-        return dw
-    x, gy = x.to(F64), gy.to(F64)
-    return one(x, gy), one(x.abs(), gy.abs())
-
-
 def _wgrad_problem(mode, shape):
     """(descriptor, gathered operand shape, other operand shape, dw shape) of the launch ops.conv_wgrad makes for this layer:
     the layer's own geometry, or -- 'c3up' -- the adjoint problem whose result is folded onto the 3x3 taps afterwards"""

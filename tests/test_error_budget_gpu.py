@@ -311,11 +311,20 @@ def test_conv_forward_dgrad_wgrad(case):
 
 @pytest.mark.parametrize("W", [8, 16, 32, 64, 128])
 def test_wgrad_widths(W):
-    """[W] the kx3 weight gradient over image widths 8 .. 128 (split-K; each run twice: atomics reorder the sums) and the
-    single-tap one (a 1x1 linear layer over the same pixels)"""
+    """[W] the weight gradient of a 3x3 layer and of a linear layer over the same pixels, image widths 8 .. 128 (split-K; each run
+    twice: atomics reorder the sums).  Which kernel each shape runs, as ops.wgrad_which reports it (asserted on the host by
+    test_wgrad_matrix_host.test_wgrad_widths_shapes_run_the_single_tap_kernel):
+      128 -> 192   tn<192,128> bkp=64 waves=8 fast=1 at every width, 3x3 and linear alike (neither kx3 tile divides the layer);
+      192 -> 192   3x3: kx3<192,96> taps=3, seg = min(W, 64), from W = 16 on (W = 8: tn<192,192>); linear: kx3<192,192> taps=1;
+      128 -> 128   3x3: kx3<128,128> taps=3, seg = min(W, 64), from W = 16 on (W = 8: tn<128,128>); linear: tn<128,128>."""
+    worst = [_wgrad_widths_layer(W, C, Co) for C, Co in ((128, 192), (192, 192), (128, 128))]
+    report(f"[W] W={W} max ratio (128->192, 192->192, 128->128)", tuple(round(v, 3) for v in worst))
+
+
+def _wgrad_widths_layer(W, C, Co):
     from transvae.hip import ops
     g = torch.Generator().manual_seed(W)
-    B, H, C, Co = 4, 64 if W <= 32 else 16, 128, 192
+    B, H = 4, 64 if W <= 32 else 16
     x = r16(torch.randn(B, H, W, C, generator=g, dtype=F64))
     w = r16(torch.randn(Co, 3, 3, C, generator=g, dtype=F64) * (9 * C) ** -0.5)
     gz = r16(torch.randn(B, H, W, Co, generator=g, dtype=F64))
@@ -329,9 +338,9 @@ def test_wgrad_widths(W):
         wl = w1.float().to(dev()).requires_grad_(True)
         ops.linear(x.reshape(-1, C).to(dev(), BF), wl).backward(gz.reshape(-1, Co).to(dev(), BF))
         torch.cuda.synchronize()
-        worst.append(check_fp32(wr.grad.cpu(), dw64, adw, WGRAD_C, f"kx3 dw W={W}"))
-        worst.append(check_fp32(wl.grad.cpu(), dl64, adl, WGRAD_C, f"one-tap dw W={W}"))
-    report(f"[W] W={W} max ratio", round(max(worst), 3))
+        worst.append(check_fp32(wr.grad.cpu(), dw64, adw, WGRAD_C, f"3x3 dw W={W} {C}->{Co}"))
+        worst.append(check_fp32(wl.grad.cpu(), dl64, adl, WGRAD_C, f"linear dw W={W} {C}->{Co}"))
+    return max(worst)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
