@@ -177,6 +177,25 @@ __global__ __launch_bounds__(256) void global_avgpool_kernel(const bf16* __restr
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// spatial rows (sFID): out[b, p * nc + c] = x[b, p, c0 + c] for p < HW, c < nc, bf16 -> fp32 (exact); zeros from HW * nc up to
+// ldo.  One thread per output element: consecutive threads write consecutive floats and read nc-element runs ldc apart.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void spatial_rows_kernel(const bf16* __restrict__ x, float* __restrict__ out, long long total, int HW, int ldc,
+                                                           int c0, int nc, int ldo) {
+    const int used = HW * nc;
+    for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+        const int col = (int)(idx % ldo);
+        const long long b = idx / ldo;
+        float v = 0.f;
+        if (col < used) {
+            const int p = col / nc, c = col - p * nc;
+            v = (float)x[((size_t)b * HW + p) * ldc + c0 + c];
+        }
+        out[idx] = v;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Streaming moments in fp64.  state = {count, unused, mean[D], M2[D * D]} with M2 = sum_i (x_i - mean)(x_i - mean)^T of the
 // samples seen so far.  A batch is merged SAMPLE BY SAMPLE, in row order, with the pairwise (Chan et al.) merge of the running
 // statistics and a single sample -- Welford's update:
@@ -281,6 +300,17 @@ extern "C" int tv_global_avgpool(const void* x, float* out, int B, int HW, int C
     const long long total = (long long)B * (C / 8);
     hipLaunchKernelGGL(global_avgpool_kernel, dim3(bw_grid(total)), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, out, total, HW, C);
     TV_CHECK_LAUNCH("tv_global_avgpool");
+    return TV_OK;
+}
+
+extern "C" int tv_spatial_rows(const void* x, int B, int HW, int C, int ldc, int c0, int nc, float* out, int ldo, void* stream) {
+    TV_CHECK_ARG(x && out && B > 0 && HW > 0 && C > 0, "tv_spatial_rows: bad arguments");
+    TV_CHECK_ARG(ldc >= C, "tv_spatial_rows: ldc=%d must be at least C=%d", ldc, C);
+    TV_CHECK_ARG(c0 >= 0 && nc >= 1 && nc <= C - c0, "tv_spatial_rows: channels c0=%d .. c0 + nc=%d - 1 must lie in [0, C=%d)", c0, nc, C);
+    TV_CHECK_ARG((long long)HW * nc <= (long long)ldo, "tv_spatial_rows: ldo=%d must be at least HW * nc = %lld", ldo, (long long)HW * nc);
+    const long long total = (long long)B * ldo;
+    hipLaunchKernelGGL(spatial_rows_kernel, dim3(bw_grid(total)), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, out, total, HW, ldc, c0, nc, ldo);
+    TV_CHECK_LAUNCH("tv_spatial_rows");
     return TV_OK;
 }
 

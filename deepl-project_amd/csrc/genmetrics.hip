@@ -1,7 +1,9 @@
-// Generation metrics (transvae/metrics_gen.py drives all three):
-//   tv_knn_radius     squared distance to the k-th nearest neighbour inside one feature set   (improved precision / recall,
-//   tv_manifold_hits  is a query inside any of the k-NN balls of a set                          Kynkaanniemi et al. 2019)
-//   tv_softmax_stats  streaming fp64 sums of p log p and of p over classifier rows            (Inception Score)
+// Generation metrics (transvae/metrics_gen.py drives them all):
+//   tv_knn_radius        squared distance to the k-th nearest neighbour inside one feature set   (improved precision / recall,
+//   tv_manifold_hits     is a query inside any of the k-NN balls of a set                          Kynkaanniemi et al. 2019)
+//   tv_ball_counts       how many balls hold a query / how many points a query's ball holds      (density / coverage, Naeem et al. 2020)
+//   tv_poly_kernel_sums  sums of (gamma x.y + c0)^3 over index-addressed subsets of rows         (KID, Binkowski et al. 2018)
+//   tv_softmax_stats     streaming fp64 sums of p log p and of p over classifier rows            (Inception Score)
 //
 // Squared distance, shared by the two pairwise kernels.  D(a, b) = sum_c (a_c - b_c)^2 as ONE fp32 chain over c = 0 .. d - 1 in
 // order: diff = a_c - b_c (one rounding), acc = fmaf(diff, diff, acc).  No partial chains: the accumulator of a (query, point) pair
@@ -19,9 +21,18 @@
 //   knn: a thread keeps a sorted list of the 8 smallest distances per query row (min / max insertion); the 16 lists of a row
 //        are merged through LDS in tx order; r2 = entry k - 1.  Self is dropped by index, points past N by index.
 //   hits: hit |= D <= r2[j] on the fp32 values; the 16 flags of a row are OR-ed through LDS.
+//   counts: count += D <= r2[j] (one radius per data point) or D <= r2[i] (one radius per query), the same comparison on the same
+//        chain; the 16 counts of a row are added through LDS, the slices by the merge launch.  Integer sums carry no order question.
 // The k smallest values of a multiset do not depend on the order they are met in, and neither does an OR: no atomics, the same bits
 // on every run and for every cut of the query range into launches.  Inputs must be finite: fminf / fmaxf drop a NaN distance and
 // repeat a list entry in its place, so a non-finite row corrupts the radii silently; the callers check.
+//
+// tv_poly_kernel_sums.  The same staging (pw_tile: loader, PW_LD layout, float4 or scalar loads, zeros past d) with the product
+// chain dot = fmaf(a_c, b_c, dot) in place of the difference chain; the rows of a tile are addressed through int32 index lists, one
+// pair of lists per subset (grid.z), so nothing is gathered and no m x m matrix exists.  Per pair, fp64 with contraction off:
+// t = (double)dot * gamma + coef0, k = (t * t) * t.  A thread adds its 16 pairs in (p, e) order, thread 0 adds the 256 thread
+// partials in thread order, and the finalise launch adds the block partials of a subset in block order: no atomics, the same bits on
+// every run and for both load paths.
 //
 // tv_softmax_stats.  One block per row: z - max, exp, p = e / s, log p = (z - max) - log s, all fp64; the row sum s and the row's
 // sum of p log p are added by one thread in k order.  A second launch adds the rows to the state one at a time in row order.
@@ -85,9 +96,66 @@ __device__ __forceinline__ float pw_kth(const f32x8& l, int k) {
     return r;
 }
 
+// One 64 x 64 tile of pairs: acc[p][e] = the chain over c = 0 .. d - 1 of the pair (row ty 4 + p of the q side, row tx 4 + e of the x
+// side).  DOT false: diff = a_c - b_c, acc = fmaf(diff, diff, acc) (squared distance); DOT true: acc = fmaf(a_c, b_c, acc) (dot
+// product).  Thread t loads rows lr = t >> 3 and lr + 32 of either side (qrow / xrow; nullptr: a row past the range, staged as zeros).
+template <bool VEC, bool DOT>
+__device__ __forceinline__ void pw_tile(const float* (&qrow)[2], const float* (&xrow)[2], int d, float* __restrict__ qs,
+                                        float* __restrict__ xs, float (&acc)[4][4]) {
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const int lr = t >> 3, lc = (t & 7) * 4;            // loader: rows lr and lr + 32, coordinates lc .. lc + 3 of the chunk
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[p][c] = 0.f;
+    f32x4 pq[2], px[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        pq[s] = pw_load<VEC>(qrow[s], lc, d);
+        px[s] = pw_load<VEC>(xrow[s], lc, d);
+    }
+    for (int c0 = 0; c0 < d; c0 += PW_C) {
+        __syncthreads();                                // the previous chunk (or the previous tile's epilogue) has been read
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                qs[(lc + e) * PW_LD + lr + 32 * s] = pq[s][e];
+                xs[(lc + e) * PW_LD + lr + 32 * s] = px[s][e];
+            }
+        __syncthreads();
+        if (c0 + PW_C < d) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                pq[s] = pw_load<VEC>(qrow[s], c0 + PW_C + lc, d);
+                px[s] = pw_load<VEC>(xrow[s], c0 + PW_C + lc, d);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < PW_C; ++c) {
+            const f32x4 a = *(const f32x4*)&qs[c * PW_LD + ty * 4];
+            const f32x4 b = *(const f32x4*)&xs[c * PW_LD + tx * 4];
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (DOT) {
+                        acc[p][e] = fmaf(a[p], b[e], acc[p][e]);
+                    } else {
+                        const float df = a[p] - b[e];
+                        acc[p][e] = fmaf(df, df, acc[p][e]);
+                    }
+                }
+        }
+    }
+}
+
 // MODE 0: knn radius (out, part: float; self = index in x of query 0).  MODE 1: hits (out, part: int; r2 per data point).
+// MODE 2 / 3: ball counts (out, part: int) with r2 per data point / per query.
+// (MODE 3 asks for two blocks per CU: left alone, the scheduler hoists LDS reads until it holds 257 registers and one wave per SIMD
+// remains, which doubles the kernel's time; the other modes settle at 176-204 on their own and are built as before)
 template <int MODE, bool VEC>
-__global__ __launch_bounds__(256) void pairwise_kernel(const float* __restrict__ q, int M, int ldq, const float* __restrict__ x, int N, int ldx,
+__global__ __launch_bounds__(256, MODE == 3 ? 2 : 1) void pairwise_kernel(const float* __restrict__ q, int M, int ldq, const float* __restrict__ x, int N, int ldx,
                                                        int d, int self, const float* __restrict__ r2, int per, int slices, int k,
                                                        void* __restrict__ out, void* __restrict__ part) {
     __shared__ __attribute__((aligned(16))) float sm[PW_T * 16 * PW_K];   // staging (2 x 32 x 68) first, the row merge afterwards
@@ -97,7 +165,7 @@ __global__ __launch_bounds__(256) void pairwise_kernel(const float* __restrict__
     const int qi0 = blockIdx.x * PW_T;
     const int jbeg = blockIdx.y * per;
     const int jend = jbeg + per < N ? jbeg + per : N;
-    const int lr = t >> 3, lc = (t & 7) * 4;            // loader: rows lr and lr + 32, coordinates lc .. lc + 3 of the chunk
+    const int lr = t >> 3;                              // loader rows lr and lr + 32 (pw_tile)
     const float* qrow[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -106,6 +174,13 @@ __global__ __launch_bounds__(256) void pairwise_kernel(const float* __restrict__
     }
     f32x8 list[4];
     bool hit[4] = {false, false, false, false};
+    int cnt[4] = {0, 0, 0, 0};
+    float rq[4] = {-1.f, -1.f, -1.f, -1.f};             // MODE 3: the radii of this thread's four queries (past the range: never stored)
+    if (MODE == 3) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+            if (qi0 + ty * 4 + p < M) rq[p] = r2[qi0 + ty * 4 + p];
+    }
 #pragma unroll
     for (int p = 0; p < 4; ++p)
 #pragma unroll
@@ -119,46 +194,7 @@ __global__ __launch_bounds__(256) void pairwise_kernel(const float* __restrict__
             xrow[s] = r < jend ? x + (size_t)r * ldx : nullptr;
         }
         float acc[4][4];
-#pragma unroll
-        for (int p = 0; p < 4; ++p)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc[p][c] = 0.f;
-        f32x4 pq[2], px[2];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            pq[s] = pw_load<VEC>(qrow[s], lc, d);
-            px[s] = pw_load<VEC>(xrow[s], lc, d);
-        }
-        for (int c0 = 0; c0 < d; c0 += PW_C) {
-            __syncthreads();                            // the previous chunk (or the previous tile's epilogue) has been read
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    qs[(lc + e) * PW_LD + lr + 32 * s] = pq[s][e];
-                    xs[(lc + e) * PW_LD + lr + 32 * s] = px[s][e];
-                }
-            __syncthreads();
-            if (c0 + PW_C < d) {
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    pq[s] = pw_load<VEC>(qrow[s], c0 + PW_C + lc, d);
-                    px[s] = pw_load<VEC>(xrow[s], c0 + PW_C + lc, d);
-                }
-            }
-#pragma unroll
-            for (int c = 0; c < PW_C; ++c) {
-                const f32x4 a = *(const f32x4*)&qs[c * PW_LD + ty * 4];
-                const f32x4 b = *(const f32x4*)&xs[c * PW_LD + tx * 4];
-#pragma unroll
-                for (int p = 0; p < 4; ++p)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float df = a[p] - b[e];
-                        acc[p][e] = fmaf(df, df, acc[p][e]);
-                    }
-            }
-        }
+        pw_tile<VEC, false>(qrow, xrow, d, qs, xs, acc);
         if (MODE == 0) {
 #pragma unroll
             for (int p = 0; p < 4; ++p)
@@ -168,13 +204,28 @@ __global__ __launch_bounds__(256) void pairwise_kernel(const float* __restrict__
                     const bool drop = j >= jend || j == self + qi0 + ty * 4 + p;   // past the range, or the query itself: by index
                     pw_insert(list[p], drop ? INFINITY : acc[p][e]);
                 }
-        } else {
+        } else if (MODE == 1) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int j = j0 + tx * 4 + e;
                 const float rj = j < jend ? r2[j] : -1.f;                         // D >= 0 > -1: a point past the range never hits
 #pragma unroll
                 for (int p = 0; p < 4; ++p) hit[p] = hit[p] || acc[p][e] <= rj;
+            }
+        } else if (MODE == 2) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int j = j0 + tx * 4 + e;
+                const float rj = j < jend ? r2[j] : -1.f;
+#pragma unroll
+                for (int p = 0; p < 4; ++p) cnt[p] += acc[p][e] <= rj ? 1 : 0;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float lim = j0 + tx * 4 + e < jend ? INFINITY : -1.f;       // a point past the range never counts: D >= 0 > -1
+#pragma unroll
+                for (int p = 0; p < 4; ++p) cnt[p] += acc[p][e] <= fminf(rq[p], lim) ? 1 : 0;
             }
         }
     }
@@ -201,7 +252,7 @@ __global__ __launch_bounds__(256) void pairwise_kernel(const float* __restrict__
 #pragma unroll
             for (int s = 0; s < PW_K; ++s) dst[s] = l[s];
         }
-    } else {
+    } else if (MODE == 1) {
         int* flags = (int*)sm;
 #pragma unroll
         for (int p = 0; p < 4; ++p) flags[(ty * 4 + p) * 16 + tx] = hit[p] ? 1 : 0;
@@ -209,6 +260,16 @@ __global__ __launch_bounds__(256) void pairwise_kernel(const float* __restrict__
         if (t >= PW_T || i >= M) return;
         int h = 0;
         for (int u = 0; u < 16; ++u) h |= flags[t * 16 + u];
+        if (slices == 1) ((int*)out)[i] = h;
+        else ((int*)part)[(size_t)i * slices + blockIdx.y] = h;
+    } else {
+        int* counts = (int*)sm;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) counts[(ty * 4 + p) * 16 + tx] = cnt[p];
+        __syncthreads();
+        if (t >= PW_T || i >= M) return;
+        int h = 0;
+        for (int u = 0; u < 16; ++u) h += counts[t * 16 + u];
         if (slices == 1) ((int*)out)[i] = h;
         else ((int*)part)[(size_t)i * slices + blockIdx.y] = h;
     }
@@ -225,10 +286,15 @@ __global__ __launch_bounds__(256) void pairwise_merge_kernel(const void* __restr
         for (int s = 0; s < PW_K; ++s) l[s] = INFINITY;
         for (int u = 0; u < slices * PW_K; ++u) pw_insert(l, src[u]);
         ((float*)out)[i] = pw_kth(l, k);
-    } else {
+    } else if (MODE == 1) {
         const int* src = (const int*)part + (size_t)i * slices;
         int h = 0;
         for (int u = 0; u < slices; ++u) h |= src[u];
+        ((int*)out)[i] = h;
+    } else {
+        const int* src = (const int*)part + (size_t)i * slices;
+        int h = 0;
+        for (int u = 0; u < slices; ++u) h += src[u];
         ((int*)out)[i] = h;
     }
 }
@@ -250,6 +316,65 @@ int pw_run(const float* q, int M, int ldq, const float* x, int N, int ldx, int d
         TV_CHECK_LAUNCH(name);
     }
     return TV_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// tv_poly_kernel_sums
+// ---------------------------------------------------------------------------------------------------------------------
+// block (bx, by, s): the pairs (i, j) of subset s with i in [64 by, 64 by + 64), j in [64 bx, 64 bx + 64); row i of the a side is
+// a[ia[s m + i]], row j of the b side b[ib[s m + j]].  part: one double per block, subset-major, then by, then bx.
+template <bool VEC>
+__global__ __launch_bounds__(256) void poly_sums_kernel(const float* __restrict__ a, int lda, const int* __restrict__ ia,
+                                                        const float* __restrict__ b, int ldb, const int* __restrict__ ib, int m, int d,
+                                                        double gamma, double coef0, int skip, double* __restrict__ part) {
+    __shared__ __attribute__((aligned(16))) float sm[2 * PW_SIDE];        // staging first, the 256 thread partials (fp64) afterwards
+    static_assert(2 * PW_SIDE * sizeof(float) >= 256 * sizeof(double), "the thread partials fit the staging buffer");
+    float* qs = sm;
+    float* xs = sm + PW_SIDE;
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const int lr = t >> 3;
+    const int i0 = blockIdx.y * PW_T, j0 = blockIdx.x * PW_T;
+    const int* sa = ia + (size_t)blockIdx.z * m;
+    const int* sb = ib + (size_t)blockIdx.z * m;
+    const float* qrow[2];
+    const float* xrow[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int i = i0 + lr + 32 * s, j = j0 + lr + 32 * s;
+        qrow[s] = i < m ? a + (size_t)sa[i] * lda : nullptr;
+        xrow[s] = j < m ? b + (size_t)sb[j] * ldb : nullptr;
+    }
+    float acc[4][4];
+    pw_tile<VEC, true>(qrow, xrow, d, qs, xs, acc);
+    double sum = 0.0;
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int i = i0 + ty * 4 + p, j = j0 + tx * 4 + e;
+            if (i < m && j < m && !(skip && i == j)) {
+                const double v = (double)acc[p][e] * gamma + coef0;
+                sum += (v * v) * v;
+            }
+        }
+    __syncthreads();                                    // staging no longer read
+    double* red = (double*)sm;
+    red[t] = sum;
+    __syncthreads();
+    if (t == 0) {
+        double s = 0.0;
+        for (int u = 0; u < 256; ++u) s += red[u];      // thread order
+        part[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+__global__ __launch_bounds__(256) void poly_finalise_kernel(const double* __restrict__ part, int per, int S, double* __restrict__ sums) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= S) return;
+    const double* src = part + (size_t)s * per;
+    double v = 0.0;
+    for (int u = 0; u < per; ++u) v += src[u];          // block order
+    sums[s] = v;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -324,6 +449,46 @@ extern "C" int tv_manifold_hits(const float* q, int M, int ldq, const float* x, 
     TV_CHECK_ARG(d >= 1 && d <= 8192, "tv_manifold_hits: d=%d must be in [1, 8192]", d);
     TV_CHECK_ARG(ldq >= d && ldx >= d, "tv_manifold_hits: ldq=%d and ldx=%d must be at least d=%d", ldq, ldx, d);
     return pw_run<1>(q, M, ldq, x, N, ldx, d, 0, r2, 0, hit, scratch, (hipStream_t)stream, "tv_manifold_hits");
+}
+
+extern "C" int tv_ball_counts(const float* q, int M, int ldq, const float* x, int N, int ldx, const float* r2, int d, int radius_of, int* count,
+                              int* scratch, void* stream) {
+    TV_CHECK_ARG(q && x && r2 && count, "tv_ball_counts: q, x, r2 and count must not be NULL");
+    TV_CHECK_ARG(M >= 1 && M <= (1 << 30), "tv_ball_counts: M=%d must be in [1, 2^30]", M);
+    TV_CHECK_ARG(N >= 1 && N <= (1 << 30), "tv_ball_counts: N=%d must be in [1, 2^30]", N);
+    TV_CHECK_ARG(d >= 1 && d <= 8192, "tv_ball_counts: d=%d must be in [1, 8192]", d);
+    TV_CHECK_ARG(ldq >= d && ldx >= d, "tv_ball_counts: ldq=%d and ldx=%d must be at least d=%d", ldq, ldx, d);
+    TV_CHECK_ARG(radius_of == 0 || radius_of == 1, "tv_ball_counts: radius_of=%d must be 0 (one radius per data point) or 1 (per query)", radius_of);
+    if (radius_of == 0) return pw_run<2>(q, M, ldq, x, N, ldx, d, 0, r2, 0, count, scratch, (hipStream_t)stream, "tv_ball_counts");
+    return pw_run<3>(q, M, ldq, x, N, ldx, d, 0, r2, 0, count, scratch, (hipStream_t)stream, "tv_ball_counts");
+}
+
+extern "C" long long tv_poly_kernel_scratch_doubles(int m, int S) {
+    if (m < 1 || m > (1 << 16) || S < 1 || S > 65535) return -1;
+    const long long tiles = tv_cdiv(m, PW_T);
+    return tiles * tiles * S;
+}
+
+extern "C" int tv_poly_kernel_sums(const float* a, int lda, const int* ia, const float* b, int ldb, const int* ib, int m, int S, int d, double gamma,
+                                   double coef0, int skip_equal_position, double* sums, double* scratch, void* stream) {
+    TV_CHECK_ARG(a && ia && b && ib && sums && scratch, "tv_poly_kernel_sums: a, ia, b, ib, sums and scratch must not be NULL");
+    TV_CHECK_ARG(m >= 1 && m <= (1 << 16), "tv_poly_kernel_sums: m=%d must be in [1, 2^16]", m);
+    TV_CHECK_ARG(S >= 1 && S <= 65535, "tv_poly_kernel_sums: S=%d must be in [1, 65535]", S);
+    TV_CHECK_ARG(d >= 1 && d <= 8192, "tv_poly_kernel_sums: d=%d must be in [1, 8192]", d);
+    TV_CHECK_ARG(lda >= d && ldb >= d, "tv_poly_kernel_sums: lda=%d and ldb=%d must be at least d=%d", lda, ldb, d);
+    const int tiles = tv_cdiv(m, PW_T);
+    const long long blocks = (long long)tiles * tiles * S;
+    TV_CHECK_ARG(blocks < (1 << 24), "tv_poly_kernel_sums: m=%d, S=%d is %lld blocks; at most 2^24 - 1 per launch", m, S, blocks);
+    hipStream_t s = (hipStream_t)stream;
+    const bool vec = ((((uintptr_t)a) | ((uintptr_t)b)) & 15) == 0 && lda % 4 == 0 && ldb % 4 == 0;
+    const dim3 grid((unsigned)tiles, (unsigned)tiles, (unsigned)S);
+    const int skip = skip_equal_position ? 1 : 0;
+    if (vec) hipLaunchKernelGGL(poly_sums_kernel<true>, grid, dim3(256), 0, s, a, lda, ia, b, ldb, ib, m, d, gamma, coef0, skip, scratch);
+    else hipLaunchKernelGGL(poly_sums_kernel<false>, grid, dim3(256), 0, s, a, lda, ia, b, ldb, ib, m, d, gamma, coef0, skip, scratch);
+    TV_CHECK_LAUNCH("tv_poly_kernel_sums");
+    hipLaunchKernelGGL(poly_finalise_kernel, dim3((unsigned)tv_cdiv(S, 256)), dim3(256), 0, s, (const double*)scratch, tiles * tiles, S, sums);
+    TV_CHECK_LAUNCH("tv_poly_kernel_sums (finalise)");
+    return TV_OK;
 }
 
 extern "C" int tv_softmax_stats(const float* logits, int B, int K, int ld, double* state, double* scratch, void* stream) {

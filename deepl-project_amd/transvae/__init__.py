@@ -30,7 +30,9 @@ integrate the velocity field with Euler steps and classifier-free guidance and d
 is behind keywords whose defaults change nothing (`cosine_weight`; `method="heun"`, `timestep_shift`, `cfg_interval`).  Generator evaluation
 (transvae/evaluate_dit.py, transvae/metrics_gen.py, csrc/genmetrics.hip): `evaluate_dit` samples, extracts Inception features and
 returns gFID, Inception Score (`InceptionScore`) and the k-NN precision / recall (`knn_radius`, `manifold_hits`,
-`precision_recall`) against a `reference_statistics` dict; `ParamEMA` (transvae/optim.py) is the weight average they are measured on,
+`precision_recall`) against a `reference_statistics` dict, and on request sFID (the spatial tap of `InceptionFeatures.features(...,
+spatial=True)`), KID (`kernel_inception_distance`, `poly_kernel_sums`, `kid_subsets`), density / coverage (`density_coverage`,
+`ball_counts`) and the Inception Score as a mean over splits (`InceptionScore(..., split_size=...)`); `ParamEMA` (transvae/optim.py) is the weight average they are measured on,
 kept by `fit_dit(..., ema_decay=...)`.  `LightningDiT` / `create_lightning_dit` (transvae/lightning_dit.py, csrc/lightning.hip, csrc/dit.hip)
 are the same model with the LightningDiT block: RMSNorm adaLN with a learned weight, per-head qk-norm before the RoPE and a SwiGLU MLP,
 each behind a switch; the training, sampling and evaluation entry points above take it unchanged.  `dit_xl` / `lightning_dit_xl` are
@@ -39,7 +41,7 @@ the XL configurations (1152 wide, 28 deep, 16 heads of head_dim 72: csrc/attenti
 """
 from .dit import DiT, create_dit, dit_xl, fit_dit, flow_matching_loss, sample_images, sample_latents
 from .evaluate import evaluate
-from .evaluate_dit import evaluate_dit
+from .evaluate_dit import ALL_METRICS, evaluate_dit
 from .hip.ops import deterministic
 from .generate import interpolate_latents, random_samples, reconstruct
 from .lightning_dit import LightningDiT, create_lightning_dit, lightning_dit_xl
@@ -51,7 +53,8 @@ from .losses.vf import DinoV2Features, VFLoss
 from .metrics import reconstruction_metrics
 from .probe import LinearProbe, fit_linear_probe, linear_probe_accuracy, probe_rows, softmax_xent
 from .metrics_fid import FrechetDistance, InceptionFeatures
-from .metrics_gen import InceptionScore, knn_radius, manifold_hits, precision_recall, reference_statistics
+from .metrics_gen import (InceptionScore, ball_counts, density_coverage, kernel_inception_distance, kid_subsets, knn_radius, manifold_hits,
+                          poly_kernel_sums, precision_recall, reference_statistics)
 from .optim import ParamEMA
 from .models.discriminator import PatchDiscriminator
 from .models.transvae import TransVAE, create_transvae
@@ -63,4 +66,5 @@ __all__ = ["TransVAE", "create_transvae", "TransVAELoss", "reconstruction_metric
            "extract_latents", "latent_points", "latent_density_metrics", "latent_space_metrics", "probe_rows", "softmax_xent", "LinearProbe",
            "fit_linear_probe", "linear_probe_accuracy", "DiT", "create_dit", "flow_matching_loss", "sample_latents", "sample_images", "fit_dit",
            "evaluate_dit", "InceptionScore", "knn_radius", "manifold_hits", "precision_recall", "reference_statistics", "ParamEMA",
-           "LightningDiT", "create_lightning_dit", "deterministic", "dit_xl", "lightning_dit_xl"]
+           "LightningDiT", "create_lightning_dit", "deterministic", "dit_xl", "lightning_dit_xl", "ball_counts", "density_coverage",
+           "kernel_inception_distance", "kid_subsets", "poly_kernel_sums", "ALL_METRICS"]

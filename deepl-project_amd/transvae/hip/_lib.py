@@ -166,6 +166,10 @@ SIGNATURES = {
     "tv_knn_radius": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "tv_manifold_hits": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _P]),
     "tv_softmax_stats": (_I, [_P, _I, _I, _I, _P, _P, _P]),
+    "tv_spatial_rows": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    "tv_ball_counts": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P]),
+    "tv_poly_kernel_scratch_doubles": (_LL, [_I, _I]),
+    "tv_poly_kernel_sums": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _I, C.c_double, C.c_double, _I, _P, _P, _P]),
 }
 
 _lib = None

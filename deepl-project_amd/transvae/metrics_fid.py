@@ -15,7 +15,8 @@ bf16 weight and fp32 bias when the weights are packed; a block's branches store 
 output (row stride `ldo`, offset pointer), so no concatenation kernel exists; the 1x7 / 7x1 / 1x3 / 3x1 convolutions are a row
 gather (`tv_gather_line`) followed by a GEMM with K = taps * C, because the convolution descriptor has one pad for both axes;
 widths that are no multiple of 32 (80, 48) are produced padded (96, 64) with zero weights.  Pools: `tv_pool3x3`; the last step is
-`tv_global_avgpool`.  Forward only, no gradient.
+`tv_global_avgpool`.  Forward only, no gradient.  `features(..., spatial=True)` also returns the sFID tap: the first 7 channels of
+`Mixed_6d.branch1x1` over the 17 x 17 grid as fp32 rows (`tv_spatial_rows`; DESIGN.md section 3.5 on which activation that is).
 
 `FrechetDistance` keeps count, mean and centred scatter matrix of both feature streams in fp64 on the device
 (`tv_fid_accumulate`: the pairwise (Chan) merge applied one sample at a time, so the statistics do not depend on the batch
@@ -40,6 +41,9 @@ from .hip import ops
 BF16 = torch.bfloat16
 BN_EPS = 1e-3
 FEATURE_DIM = 2048
+SPATIAL_BLOCK, SPATIAL_CHANNELS = "Mixed_6d", 7      # the sFID tap: the first 7 channels of this block's 1x1 branch
+SPATIAL_DIM = 17 * 17 * SPATIAL_CHANNELS             # 2023 values per image, (h, w, c) order
+SPATIAL_LD = 2048                                    # the row width: the next multiple of 64 (tv_fid_accumulate), zero-filled
 _BN_PARTS = (("bn.weight", "gamma"), ("bn.bias", "beta"), ("bn.running_mean", "mean"), ("bn.running_var", "var"))
 
 
@@ -185,6 +189,17 @@ def global_avgpool(x: torch.Tensor) -> torch.Tensor:
     B, H, W, Cc = x.shape
     y = torch.empty((B, Cc), dtype=torch.float32, device=x.device)
     L.check(L.load().tv_global_avgpool(ops._p(x), ops._p(y), B, H * W, Cc, ops._stream()), "tv_global_avgpool")
+    return y
+
+
+def spatial_rows(x: torch.Tensor, c0: int, nc: int, ldo: int) -> torch.Tensor:
+    """[B, H, W, C] bf16 -> [B, ldo] fp32: channels [c0, c0 + nc) of every position in (h, w, c) order, zeros from H * W * nc on."""
+    ops._need_gpu(x)
+    ops._require(x.dim() == 4 and x.dtype == BF16 and x.is_contiguous(), "spatial_rows: contiguous bf16 NHWC")
+    B, H, W, Cc = x.shape
+    ops._require(0 <= c0 and nc >= 1 and c0 + nc <= Cc and H * W * nc <= ldo, "spatial_rows: channel range or row width does not fit")
+    y = torch.empty((B, ldo), dtype=torch.float32, device=x.device)
+    L.check(L.load().tv_spatial_rows(ops._p(x), B, H * W, Cc, Cc, int(c0), int(nc), ops._p(y), int(ldo), ops._stream()), "tv_spatial_rows")
     return y
 
 
@@ -376,7 +391,7 @@ class InceptionFeatures(nn.Module):
         self._conv(pool3x3(x, pool_mode), f"{blk}.branch_pool", y, 1856)
         return y
 
-    def _run(self, a, b, clip):
+    def _run(self, a, b, clip, spatial=False):
         cols = fid_prep(a, b, clip)                                          # [B, 149, 149, 32]
         B = cols.shape[0]
         wb, bias = self.packed("Conv2d_1a_3x3")
@@ -395,16 +410,21 @@ class InceptionFeatures(nn.Module):
         h = self._inception_a(h, "Mixed_5c", 64)
         h = self._inception_a(h, "Mixed_5d", 64)
         h = self._inception_b(h, "Mixed_6a")                                 # 17
+        sp = None
         for blk in ("Mixed_6b", "Mixed_6c", "Mixed_6d", "Mixed_6e"):
             h = self._inception_c(h, blk)
+            if spatial and blk == SPATIAL_BLOCK:                             # branch1x1 sits at column 0 of the block's output
+                sp = spatial_rows(h, 0, SPATIAL_CHANNELS, SPATIAL_LD)
         h = self._inception_d(h, "Mixed_7a")                                 # 8
         h = self._inception_e(h, "Mixed_7b", L.POOL3_AVG_S1P1)
         h = self._inception_e(h, "Mixed_7c", L.POOL3_MAX_S1P1)
-        return global_avgpool(h)
+        return (global_avgpool(h), sp) if spatial else global_avgpool(h)
 
     @torch.no_grad()
-    def features(self, a: torch.Tensor, b: Optional[torch.Tensor] = None, clip: bool = False) -> torch.Tensor:
-        """[Ba (+ Bb), 2048] fp32 features of the images `a` (then `b`) as ONE batch; clip=True clamps the pixels to [0, 1]."""
+    def features(self, a: torch.Tensor, b: Optional[torch.Tensor] = None, clip: bool = False, spatial: bool = False):
+        """[Ba (+ Bb), 2048] fp32 features of the images `a` (then `b`) as ONE batch; clip=True clamps the pixels to [0, 1].
+        spatial=True returns (pool3 [n, 2048], spatial [n, SPATIAL_LD]): the second holds the sFID tap, the first SPATIAL_CHANNELS
+        channels of `SPATIAL_BLOCK.branch1x1` over the 17 x 17 grid in (h, w, c) order (SPATIAL_DIM values) and zeros after them."""
         for t in (a,) if b is None else (a, b):
             if t.dim() != 4 or t.shape[1] != 3 or t.shape[0] == 0 or t.shape[2] < 8 or t.shape[3] < 8:
                 raise ValueError(f"InceptionFeatures: images must be a non-empty [B, 3, H, W] with H, W >= 8, got {tuple(t.shape)}")
@@ -419,9 +439,11 @@ class InceptionFeatures(nn.Module):
         with torch.cuda.device(a.device), torch.autocast("cuda", enabled=False):
             n = a.shape[0] + (0 if b is None else b.shape[0])
             if n <= self.MAX_BATCH:
-                return self._run(a, b, clip)
-            parts = [self._run(t[i:i + self.MAX_BATCH], None, clip) for t in ((a,) if b is None else (a, b))
+                return self._run(a, b, clip, spatial)
+            parts = [self._run(t[i:i + self.MAX_BATCH], None, clip, spatial) for t in ((a,) if b is None else (a, b))
                      for i in range(0, t.shape[0], self.MAX_BATCH)]
+            if spatial:
+                return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
             return torch.cat(parts)
 
     def forward(self, images: torch.Tensor) -> torch.Tensor:

@@ -479,6 +479,11 @@ int tv_pool3x3(const void* x, void* y, int B, int H, int W, int C, int ldo, int 
 int tv_gather_line(const void* x, void* y, int B, int H, int W, int C, int taps, int axis, void* stream);
 /* Global average pool: x [B, HW, C] bf16 -> out [B, C] fp32; pixels summed in order in fp64, one rounding.  C % 8 == 0. */
 int tv_global_avgpool(const void* x, float* out, int B, int HW, int C, void* stream);
+/* Spatial feature rows (sFID): x [B, HW, ldc] bf16 with C <= ldc channels per position -> out [B, ldo] fp32 with
+ * out[b, p * nc + c] = x[b, p, c0 + c] for p < HW, c < nc (the (h, w, c) flattening of a channel range; bf16 -> fp32 is exact) and
+ * zeros in the columns HW * nc .. ldo - 1.  0 <= c0, c0 + nc <= C, HW * nc <= ldo.  Zero columns have zero mean and zero scatter, so
+ * rows padded to a multiple of 64 go through tv_fid_accumulate and the caller trims the statistics to HW * nc. */
+int tv_spatial_rows(const void* x, int B, int HW, int C, int ldc, int c0, int nc, float* out, int ldo, void* stream);
 /* Streaming first and second moments of feature rows, fp64 on the device.
  * state: tv_fid_state_doubles(D) doubles (-1: D must be a multiple of 64 up to 8192), zero-initialised by the caller:
  * {count, unused, mean[D], M2[D * D]}, M2 the centred scatter matrix sum (x - mean)(x - mean)^T.  x [B, D] fp32 with row stride ldx;
@@ -741,6 +746,25 @@ int tv_qknorm_rope_bwd_hd(const void* qkv, const float* wq, const float* wk, voi
 int tv_knn_radius(const float* x, int N, int d, int ldx, int i0, int M, int k, float* r2, float* scratch, void* stream);
 int tv_manifold_hits(const float* q, int M, int ldq, const float* x, int N, int ldx, const float* r2, int d, int* hit, int* scratch,
                      void* stream);
+/* Ball counts (density / coverage, Naeem et al. 2020) on the same distance chain and the same `<=` on the fp32 values:
+ *   radius_of = 0: count[i] = #{j < N : D(q_i, x_j) <= r2[j]}, r2 [N], one squared radius per data point;
+ *   radius_of = 1: count[i] = #{j < N : D(q_i, x_j) <= r2[i]}, r2 [M], one squared radius per query.
+ * count int32 [M].  scratch: 32 * M ints under the rule of tv_manifold_hits; the slices are added by the merge launch (integers: no
+ * order question).  count[i] > 0 at radius_of = 0 is tv_manifold_hits' hit[i]. */
+int tv_ball_counts(const float* q, int M, int ldq, const float* x, int N, int ldx, const float* r2, int d, int radius_of, int* count,
+                   int* scratch, void* stream);
+/* Polynomial-kernel sums (KID): for every subset s < S, sums[s] = sum over 0 <= i, j < m of k(a[ia[s m + i]], b[ib[s m + j]]), the
+ * pairs with i == j left out when skip_equal_position != 0.  a, b: fp32 rows with strides lda, ldb >= d; ia, ib: int32 [S, m] row
+ * indices, which the CALLER keeps inside a and b (they are read on the device and cannot be checked here).  Nothing is gathered and
+ * no m x m matrix is formed; one launch covers all subsets, 64 x 64 pairs per block through the staging of the pairwise kernels.
+ * k(x, y): dot = ONE fp32 chain over c = 0 .. d - 1 in order, dot = fmaf(x_c, y_c, dot), the accumulator in a register across the
+ * d-chunks; then fp64 without contraction, t = (double)dot * gamma + coef0, k = (t * t) * t.  A thread adds its pairs in a fixed
+ * order, a block its threads in thread order, a second launch the blocks of a subset in block order: no atomics, the same bits on
+ * every run and for float4 and scalar loads.  scratch: tv_poly_kernel_scratch_doubles(m, S) doubles (-1: 1 <= m <= 2^16,
+ * 1 <= S <= 65535).  Bound against fp64 per sum: sum_pairs 3 t^2 gamma (d + 2) u sum_c |x_c y_c|. */
+long long tv_poly_kernel_scratch_doubles(int m, int S);
+int tv_poly_kernel_sums(const float* a, int lda, const int* ia, const float* b, int ldb, const int* ib, int m, int S, int d, double gamma,
+                        double coef0, int skip_equal_position, double* sums, double* scratch, void* stream);
 /* Softmax statistics of fp32 logits [B, K] (row stride ld >= K, 1 <= K <= 4096) for the Inception Score.  state: 2 + K doubles
  * {rows, sum_rows sum_k p log p, sum_rows p_k} that the call ADDS to (zero it to start).  Everything after the load is fp64: z - max,
  * exp, the row sum s in k order, log, p = e / s, log p = (z - max) - log s, the row's sum of p log p in k order.  The rows are added
