@@ -1,5 +1,6 @@
 // The head_dim 72 kernel family (DiT-XL / LightningDiT-XL: 1152 = 16 heads of 72): flash attention forward and backward, the
-// in-place RoPE and the qk-norm pair.  A first, sound form: plain LDS staging between two __syncthreads per tile, no DMA ring.
+// in-place RoPE.  The qk-norm pair of this head_dim (tv_qknorm_rope_fwd_hd / _bwd_hd) is qk_norm.hip, one template with head_dim 64's;
+// its summation orders are stated there and below.  A first, sound form: plain LDS staging between two __syncthreads per tile, no DMA ring.
 // DESIGN.md section 3.1 row Y holds the rounding contract; tv_*_hd in include/transvae_hip.h are the entries.
 //
 // Data: qkv [B, N, 3, heads, 72] bf16, o [B, N, heads, 72] bf16, lse [B, heads, N] fp32 (natural log), delta [2, B, heads, N] fp32
@@ -483,160 +484,6 @@ __global__ __launch_bounds__(256) void rope_qk72_kernel(bf16* __restrict__ qkv, 
     }
 }
 
-// ---- per-head RMSNorm of q and k with the 2-D RoPE ----------------------------------------------------------------------------
-constexpr int QK_LANES = 16;        // lanes of a group: 0..8 hold one piece each, 9..15 hold zeros and touch no memory
-constexpr int QK_GROUPS = 16;       // head vectors per block pass (256 threads / 16 lanes)
-constexpr int QK_MAX_BLOCKS = 1024;
-constexpr int QK_FIN_LANES = 64;    // block lanes of the dwq / dwk finalise
-constexpr float INV_HD = 1.0f / 72.0f;
-
-__device__ __forceinline__ float group16_sum(float v) {
-#pragma unroll
-    for (int o = 1; o < QK_LANES; o <<= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// A lane group takes one third of one token, unit u = token * nwhich + which, and walks its heads with the token's table row in
-// registers.  nwhich = 3 out of place (the v third is copied), 2 in place.  in and out may alias: a vector belongs to one lane
-// group, which reads it whole (the butterfly needs every live lane's load) before any of its lanes stores.
-__global__ __launch_bounds__(256) void qknorm72_rope_fwd_kernel(const bf16* in, const float* __restrict__ wq, const float* __restrict__ wk,
-                                                                const float* __restrict__ tab, bf16* out, long long units, int nwhich, int N, int heads,
-                                                                float eps) {
-    const int l16 = threadIdx.x & (QK_LANES - 1), grp = threadIdx.x >> 4;
-    const bool live = l16 < HP;
-    float wqv[8], wkv[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        wqv[e] = live ? wq[l16 * 8 + e] : 0.f;
-        wkv[e] = live ? wk[l16 * 8 + e] : 0.f;
-    }
-    for (long long base = (long long)blockIdx.x * QK_GROUPS; base < units; base += (long long)gridDim.x * QK_GROUPS) {   // (block-uniform)
-        const long long u = base + grp;
-        if (u >= units) continue;                              // (uniform over the lane group: its butterfly stays whole)
-        const long long tok = u / nwhich;
-        const int which = (int)(u - tok * nwhich);
-        const size_t off = ((size_t)(tok * 3 + which) * heads) * HD + (live ? l16 : 0) * 8;
-        if (which == 2) {                                      // v: bit for bit
-            if (live)
-                for (int hd = 0; hd < heads; ++hd) *(bf16x8*)(out + off + (size_t)hd * HD) = *(const bf16x8*)(in + off + (size_t)hd * HD);
-            continue;
-        }
-        f32x4 c1 = {1.f, 1.f, 1.f, 1.f}, s1 = {0.f, 0.f, 0.f, 0.f}, c2 = c1, s2 = s1;
-        if (tab && live) {
-            const float* tb = tab + (size_t)(tok % N) * (2 * HD) + l16 * 4;
-            c1 = *(const f32x4*)(tb), s1 = *(const f32x4*)(tb + 36), c2 = *(const f32x4*)(tb + 72), s2 = *(const f32x4*)(tb + 108);
-        }
-        for (int hd = 0; hd < heads; ++hd) {
-            bf16x8 t = zero8();
-            if (live) t = *(const bf16x8*)(in + off + (size_t)hd * HD);
-            float x[8], ss = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                x[e] = (float)t[e];
-                ss = fmaf(x[e], x[e], ss);
-            }
-            const float r = rsqrtf(group16_sum(ss) * INV_HD + eps);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = (x[e] * r) * (which == 0 ? wqv[e] : wkv[e]);
-            bf16x8 o;
-            if (tab) {
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const float a = x[2 * p], bb = x[2 * p + 1];
-                    o[2 * p] = (bf16)(a * c1[p] - bb * s1[p]);
-                    o[2 * p + 1] = (bf16)(a * s2[p] + bb * c2[p]);
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] = (bf16)x[e];
-            }
-            if (live) *(bf16x8*)(out + off + (size_t)hd * HD) = o;
-        }
-    }
-}
-
-// head vector u of the q and k thirds: token = u / (2 heads), which = (u / heads) % 2
-__global__ __launch_bounds__(256) void qknorm72_rope_bwd_kernel(const bf16* __restrict__ qkv, const float* __restrict__ wq, const float* __restrict__ wk,
-                                                                bf16* __restrict__ dqkv, float* __restrict__ part, long long units, int heads, float eps) {
-    __shared__ float s_acc[QK_GROUPS][2 * HD];
-    const int l16 = threadIdx.x & (QK_LANES - 1), grp = threadIdx.x >> 4;
-    const bool lane_live = l16 < HP;
-    float wqv[8], wkv[8], aq[8], ak[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        wqv[e] = lane_live ? wq[l16 * 8 + e] : 0.f;
-        wkv[e] = lane_live ? wk[l16 * 8 + e] : 0.f;
-        aq[e] = ak[e] = 0.f;
-    }
-    for (long long base = (long long)blockIdx.x * QK_GROUPS; base < units; base += (long long)gridDim.x * QK_GROUPS) {   // (block-uniform)
-        const long long u = base + grp;
-        const bool live = u < units && lane_live;
-        const long long th = live ? u / heads : 0;
-        const int head = live ? (int)(u - th * heads) : 0;
-        const int which = (int)(th & 1);
-        const size_t off = ((size_t)((th >> 1) * 3 + which) * heads + head) * HD + (live ? l16 : 0) * 8;
-        bf16x8 t = zero8(), dv = zero8();
-        if (live) {
-            t = *(const bf16x8*)(qkv + off);
-            dv = *(const bf16x8*)(dqkv + off);
-        }
-        float x[8], g[8], ss = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            x[e] = (float)t[e];
-            ss = fmaf(x[e], x[e], ss);
-        }
-        const float r = rsqrtf(group16_sum(ss) * INV_HD + eps);
-        float m = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float d = (float)dv[e];
-            x[e] *= r;                                          // qh
-            g[e] = d * (which == 0 ? wqv[e] : wkv[e]);
-            m = fmaf(g[e], x[e], m);
-            const float pr = d * x[e];
-            aq[e] += which == 0 ? pr : 0.f;
-            ak[e] += which == 0 ? 0.f : pr;
-        }
-        m = group16_sum(m) * INV_HD;
-        bf16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = (bf16)(r * fmaf(-x[e], m, g[e]));
-        if (live) *(bf16x8*)(dqkv + off) = o;
-    }
-    if (lane_live) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            s_acc[grp][l16 * 8 + e] = aq[e];
-            s_acc[grp][HD + l16 * 8 + e] = ak[e];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 * HD) {
-        float a = 0.f;
-        for (int gI = 0; gI < QK_GROUPS; ++gI) a += s_acc[gI][threadIdx.x];
-        part[(size_t)blockIdx.x * (2 * HD) + threadIdx.x] = a;
-    }
-}
-
-// out[j] (j < 72: dwq, else dwk) = sum over the blocks of part[block][j]: block k in lane k % 64 in order, then the lanes in order.
-// One launch block is 16 columns x 64 block lanes; 9 launch blocks cover the 144 columns.
-__global__ __launch_bounds__(1024) void qknorm72_finalize_kernel(const float* __restrict__ part, int nblk, float* __restrict__ dwq, float* __restrict__ dwk) {
-    __shared__ float s_acc[QK_FIN_LANES][16];
-    const int col = threadIdx.x & 15, bl = threadIdx.x >> 4;
-    const int j = blockIdx.x * 16 + col;
-    float a = 0.f;
-#pragma unroll 4
-    for (int k = bl; k < nblk; k += QK_FIN_LANES) a += part[(size_t)k * (2 * HD) + j];
-    s_acc[bl][col] = a;
-    __syncthreads();
-    if (bl == 0) {
-        float t = 0.f;
-        for (int i = 0; i < QK_FIN_LANES; ++i) t += s_acc[i][col];
-        if (j < HD) dwq[j] = t; else dwk[j - HD] = t;
-    }
-}
-
 int hd_check(const char* name, int B, int N, int heads, int head_dim) {
     if (head_dim != HD) {
         tv_set_error("%s: head_dim=%d is not supported (72 only; head_dim 64 has its own entries)", name, head_dim);
@@ -647,11 +494,6 @@ int hd_check(const char* name, int B, int N, int heads, int head_dim) {
         return TV_ERR_ARG;
     }
     return TV_OK;
-}
-
-int qk_blocks(long long units) {
-    const long long blocks = (units + QK_GROUPS - 1) / QK_GROUPS;
-    return (int)(blocks < QK_MAX_BLOCKS ? blocks : QK_MAX_BLOCKS);
 }
 
 unsigned attn_grid(int B, int N, int heads) { return (unsigned)((long long)tv_cdiv(N, 128) * heads * B); }
@@ -702,42 +544,5 @@ extern "C" int tv_rope_qk_hd(void* qkv, const float* tab, int B, int N, int head
     hipLaunchKernelGGL(rope_qk72_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, (bf16*)qkv, tab, total, N, heads,
                        transpose);
     TV_CHECK_LAUNCH("tv_rope_qk_hd");
-    return TV_OK;
-}
-
-extern "C" int tv_qknorm_rope_fwd_hd(const void* qkv, const float* wq, const float* wk, const float* rope_tab, void* out, int B, int N, int heads,
-                                     int head_dim, float eps, void* stream) {
-    if (int rc = hd_check("tv_qknorm_rope_fwd_hd", B, N, heads, head_dim)) return rc;
-    TV_CHECK_ARG(qkv && wq && wk && out, "tv_qknorm_rope_fwd_hd: null pointer");
-    TV_CHECK_ARG((((uintptr_t)qkv | (uintptr_t)out | (uintptr_t)rope_tab) & 15) == 0, "tv_qknorm_rope_fwd_hd: qkv / out / rope_tab must be 16-byte aligned");
-    const long long bytes = (long long)B * N * 3 * heads * HD * 2;
-    const char *a = (const char*)qkv, *b = (const char*)out;
-    TV_CHECK_ARG(a == b || a + bytes <= b || b + bytes <= a, "tv_qknorm_rope_fwd_hd: out must be qkv itself or not overlap it");
-    const int nwhich = qkv == out ? 2 : 3;
-    const long long units = (long long)B * N * nwhich;
-    hipLaunchKernelGGL(qknorm72_rope_fwd_kernel, dim3(qk_blocks(units)), dim3(256), 0, (hipStream_t)stream, (const bf16*)qkv, wq, wk, rope_tab, (bf16*)out,
-                       units, nwhich, N, heads, eps);
-    TV_CHECK_LAUNCH("tv_qknorm_rope_fwd_hd");
-    return TV_OK;
-}
-
-extern "C" long long tv_qknorm_rope_bwd_hd_partial_count(int B, int N, int heads, int head_dim) {
-    if (B <= 0 || N <= 0 || heads <= 0 || head_dim != HD) return -1;
-    return (long long)qk_blocks((long long)B * N * 2 * heads) * (2 * HD);          // floats
-}
-
-extern "C" int tv_qknorm_rope_bwd_hd(const void* qkv, const float* wq, const float* wk, void* dqkv, float* dwq, float* dwk, float* partials, int B, int N,
-                                     int heads, int head_dim, float eps, void* stream) {
-    if (int rc = hd_check("tv_qknorm_rope_bwd_hd", B, N, heads, head_dim)) return rc;
-    TV_CHECK_ARG(qkv && wq && wk && dqkv && dwq && dwk && partials, "tv_qknorm_rope_bwd_hd: null pointer");
-    TV_CHECK_ARG((((uintptr_t)qkv | (uintptr_t)dqkv) & 15) == 0, "tv_qknorm_rope_bwd_hd: qkv / dqkv must be 16-byte aligned");
-    TV_CHECK_ARG(qkv != dqkv, "tv_qknorm_rope_bwd_hd: dqkv must not be qkv");
-    const long long units = (long long)B * N * 2 * heads;
-    const int nblk = qk_blocks(units);
-    hipLaunchKernelGGL(qknorm72_rope_bwd_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const bf16*)qkv, wq, wk, (bf16*)dqkv, partials, units, heads,
-                       eps);
-    TV_CHECK_LAUNCH("tv_qknorm_rope_bwd_hd");
-    hipLaunchKernelGGL(qknorm72_finalize_kernel, dim3(2 * HD / 16), dim3(1024), 0, (hipStream_t)stream, (const float*)partials, nblk, dwq, dwk);
-    TV_CHECK_LAUNCH("tv_qknorm_rope_bwd_hd (finalise)");
     return TV_OK;
 }

@@ -1204,66 +1204,44 @@ def rms_ln_hat(x, w, eps_rms: float = 1e-6, eps_ln: float = 1e-5):
 # ---------------------------------------------------------------------------------------------
 # attention (RoPE + flash attention; head_dim 64, and 72 through the tv_*_hd entries)
 # ---------------------------------------------------------------------------------------------
+def hd_call(name: str, head_dim: int, ptrs, B: int, N: int, heads: int, *rest):
+    """Launch the per-head entry `name(*ptrs, B, N, heads, *rest, stream)` at `head_dim`: the plain entry at 64; at 72 its `_hd`
+    form, which takes `head_dim` after `heads` (where every `_hd` entry has it)."""
+    lib = L.load()
+    if head_dim == 64:
+        L.check(getattr(lib, name)(*ptrs, B, N, heads, *rest, _stream()), name)
+    else:
+        L.check(getattr(lib, name + "_hd")(*ptrs, B, N, heads, head_dim, *rest, _stream()), name + "_hd")
+
+
+def check_qkv(qkv, rope_tab, heads: int, head_dim: int, what: str):
+    """The operand checks of the attention entries: contiguous bf16 qkv [B, N, 3 * heads * head_dim], and a contiguous fp32 table
+    [N, 4, head_dim // 2] on the same device (or None).  `head_dim` is 64 or 72."""
+    _require(head_dim in (64, 72), f"{what}: head_dim={head_dim} must be 64 or 72")
+    _need_gpu(qkv)
+    _require(qkv.dtype == BF16 and qkv.is_contiguous() and qkv.dim() == 3, f"{what}: contiguous bf16 qkv [B, N, 3 C]")
+    _require(qkv.shape[2] == 3 * heads * head_dim, f"{what}: the last axis must be 3 * heads * head_dim (head_dim = {head_dim})")
+    if rope_tab is not None:
+        _require(rope_tab.dtype == torch.float32 and tuple(rope_tab.shape) == (qkv.shape[1], 4, head_dim // 2) and rope_tab.is_contiguous() and
+                 rope_tab.device == qkv.device, f"{what}: the RoPE table must be contiguous fp32 [N, 4, {head_dim // 2}] on the rows' device")
+
+
 class AttentionFn(torch.autograd.Function):
-    """qkv: [B, N, 3*C] bf16 (q | k | v, each [heads, 64]); returns o [B, N, C].
+    """qkv: [B, N, 3*C] bf16 (q | k | v, each [heads, head_dim]), table [N, 4, head_dim // 2] or None; returns o [B, N, C].
 
     RoPE is applied IN PLACE on the q and k thirds of `qkv` (the caller must not reuse the
     un-rotated projections); the backward applies the adjoint to dq, dk.
     """
 
     @staticmethod
-    def forward(ctx, qkv, rope_tab, heads: int, scale: float):
-        _need_gpu(qkv)
-        _require(qkv.dtype == BF16 and qkv.is_contiguous() and qkv.dim() == 3, "operand check failed: qkv.dtype == BF16 and qkv.is_contiguous() and qkv.dim() == 3")
-        B, N, C3 = qkv.shape
-        _require(C3 == 3 * heads * 64, "operand check failed: C3 == 3 * heads * 64")
-        lib = L.load()
-        if rope_tab is not None:
-            _require(rope_tab.dtype == torch.float32 and rope_tab.shape == (N, 4, 32) and rope_tab.is_contiguous(), "operand check failed: rope_tab.dtype == torch.float32 and rope_tab.shape == (N, 4, 32) and rope_tab.is_contiguous()")
-            L.check(lib.tv_rope_qk(_p(qkv), _p(rope_tab), B, N, heads, 0, _stream()), "tv_rope_qk")
-        o = torch.empty((B, N, heads * 64), dtype=BF16, device=qkv.device)
-        lse = torch.empty((B, heads, N), dtype=torch.float32, device=qkv.device)
-        L.check(lib.tv_attn_fwd(_p(qkv), _p(o), _p(lse), B, N, heads, scale, _stream()), "tv_attn_fwd")
-        ctx.heads, ctx.scale = heads, scale
-        ctx.save_for_backward(qkv, o, lse, rope_tab)
-        return o
-
-    @staticmethod
-    def backward(ctx, go):
-        qkv, o, lse, rope_tab = ctx.saved_tensors
-        B, N, _ = qkv.shape
-        heads = ctx.heads
-        lib = L.load()
-        go = go.contiguous()
-        delta = torch.empty((2, B, heads, N), dtype=torch.float32, device=qkv.device)   # scratch: -delta, -lse log2(e)
-        dqkv = torch.empty_like(qkv)
-        L.check(lib.tv_attn_bwd(_p(qkv), _p(o), _p(go), _p(lse), _p(delta), None, _p(dqkv), B, N, heads, ctx.scale, _stream()),
-                "tv_attn_bwd")
-        if rope_tab is not None:
-            L.check(lib.tv_rope_qk(_p(dqkv), _p(rope_tab), B, N, heads, 1, _stream()), "tv_rope_qk")
-        return dqkv, None, None, None
-
-
-class AttentionHdFn(torch.autograd.Function):
-    """`AttentionFn` at head_dim 72 (csrc/attention_hd.hip): qkv [B, N, 3*C] bf16 (q | k | v, each [heads, 72]), table [N, 4, 36].
-
-    RoPE is applied IN PLACE on the q and k thirds of `qkv`; the backward hands the table to tv_attn_bwd_hd, which stores dq / dk
-    as gradients of the un-rotated projections (the adjoint on the fp32 sums, one rounding)."""
-
-    @staticmethod
     def forward(ctx, qkv, rope_tab, heads: int, scale: float, head_dim: int):
-        _need_gpu(qkv)
-        _require(qkv.dtype == BF16 and qkv.is_contiguous() and qkv.dim() == 3, "operand check failed: qkv.dtype == BF16 and qkv.is_contiguous() and qkv.dim() == 3")
-        B, N, C3 = qkv.shape
-        _require(C3 == 3 * heads * head_dim, f"operand check failed: C3 == 3 * heads * head_dim (head_dim = {head_dim})")
-        lib = L.load()
+        check_qkv(qkv, rope_tab, heads, head_dim, "attention")
+        B, N, _ = qkv.shape
         if rope_tab is not None:
-            _require(rope_tab.dtype == torch.float32 and rope_tab.shape == (N, 4, head_dim // 2) and rope_tab.is_contiguous() and
-                     rope_tab.device == qkv.device, f"operand check failed: rope_tab contiguous fp32 (N, 4, {head_dim // 2}) on the rows' device")
-            L.check(lib.tv_rope_qk_hd(_p(qkv), _p(rope_tab), B, N, heads, head_dim, 0, _stream()), "tv_rope_qk_hd")
+            hd_call("tv_rope_qk", head_dim, (_p(qkv), _p(rope_tab)), B, N, heads, 0)
         o = torch.empty((B, N, heads * head_dim), dtype=BF16, device=qkv.device)
         lse = torch.empty((B, heads, N), dtype=torch.float32, device=qkv.device)
-        L.check(lib.tv_attn_fwd_hd(_p(qkv), _p(o), _p(lse), B, N, heads, head_dim, scale, _stream()), "tv_attn_fwd_hd")
+        hd_call("tv_attn_fwd", head_dim, (_p(qkv), _p(o), _p(lse)), B, N, heads, scale)
         ctx.args = (heads, scale, head_dim)
         ctx.save_for_backward(qkv, o, lse, rope_tab)
         return o
@@ -1276,18 +1254,21 @@ class AttentionHdFn(torch.autograd.Function):
         go = go.contiguous()
         delta = torch.empty((2, B, heads, N), dtype=torch.float32, device=qkv.device)   # scratch: -delta, -lse log2(e)
         dqkv = torch.empty_like(qkv)
-        L.check(L.load().tv_attn_bwd_hd(_p(qkv), _p(o), _p(go), _p(lse), _p(delta), _p(rope_tab), _p(dqkv), B, N, heads, head_dim, scale,
-                                        _stream()), "tv_attn_bwd_hd")
+        # The one place where the two head dims launch differently.  At 72 the table goes into tv_attn_bwd_hd, which applies the
+        # adjoint to the fp32 sums (one rounding); at 64 tv_attn_bwd runs without it and tv_rope_qk transposes the rounded dq / dk
+        # (two roundings, one more launch).  Moving 64 to the fused adjoint would change its bits.
+        fused_adjoint = head_dim != 64
+        hd_call("tv_attn_bwd", head_dim, (_p(qkv), _p(o), _p(go), _p(lse), _p(delta), _p(rope_tab) if fused_adjoint else None, _p(dqkv)),
+                B, N, heads, scale)
+        if rope_tab is not None and not fused_adjoint:
+            hd_call("tv_rope_qk", head_dim, (_p(dqkv), _p(rope_tab)), B, N, heads, 1)
         return dqkv, None, None, None, None
 
 
 def attention(qkv, rope_tab, heads: int, scale: float, head_dim: int = 64):
     """RoPE + flash attention.  `head_dim` is 64 or 72 and is never inferred from the shapes: 72 takes the kernels of
     csrc/attention_hd.hip and a table [N, 4, 36]."""
-    if head_dim == 64:
-        return AttentionFn.apply(qkv, rope_tab, heads, scale)
-    _require(head_dim == 72, f"attention: head_dim={head_dim} must be 64 or 72")
-    return AttentionHdFn.apply(qkv, rope_tab, int(heads), float(scale), 72)
+    return AttentionFn.apply(qkv, rope_tab, int(heads), float(scale), int(head_dim))
 
 
 # ---------------------------------------------------------------------------------------------

@@ -7,8 +7,8 @@ a TODO there).  `LightningDiT` is `DiT` with three switches, each of which repla
     use_qknorm    per-head RMSNorm of q and k before the 2-D RoPE                                   `qk_norm_rope_attention`
     use_swiglu    w3(silu(x1) x2), [x1 | x2] = w12(x), inner width (2 int(C mlp_ratio)) // 3         `swiglu`
 
-`adaln_rms` is the RMS form of the adaLN kernel pair in csrc/dit.hip, the other two pairs are csrc/lightning.hip (the qk-norm pair at
-head_dim 72, `LightningDiT(..., head_dim=72)` / `lightning_dit_xl`, is csrc/attention_hd.hip); everything else
+`adaln_rms` is the RMS form of the adaLN kernel pair in csrc/dit.hip, the qk-norm pair is csrc/qk_norm.hip (one kernel family for
+head_dim 64 and 72, `LightningDiT(..., head_dim=72)` / `lightning_dit_xl`), the SwiGLU pair csrc/lightning.hip; everything else
 (embedders, conditioning path, padding, RoPE table, token GEMMs, attention at head_dim 64 or 72, gate + residual, the flow-matching edge,
 `flow_matching_loss` / `sample_latents` / `fit_dit` / `evaluate_dit`) is what `DiT` uses, unchanged.  With a switch off that part of the
 block is the DiT path.  There is no CPU fallback: host tensors raise.
@@ -39,70 +39,19 @@ def _check_weight(w: torch.Tensor, n: int, like: torch.Tensor, what: str):
 
 
 class _QkNormRopeAttnFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, qkv, wq, wk, rope_tab, heads, scale, eps, keep_raw):
-        ops._need_gpu(qkv)
-        ops._require(qkv.dtype == torch.bfloat16 and qkv.is_contiguous() and qkv.dim() == 3, "qk_norm_rope_attention: contiguous bf16 qkv [B, N, 3 C]")
-        B, N, C3 = qkv.shape
-        ops._require(C3 == 3 * heads * 64, "qk_norm_rope_attention: the last axis must be 3 * heads * 64")
-        _check_weight(wq, 64, qkv, "qk_norm_rope_attention: q_norm")
-        _check_weight(wk, 64, qkv, "qk_norm_rope_attention: k_norm")
-        if rope_tab is not None:
-            ops._require(rope_tab.dtype == torch.float32 and tuple(rope_tab.shape) == (N, 4, 32) and rope_tab.is_contiguous() and
-                         rope_tab.device == qkv.device, "qk_norm_rope_attention: the RoPE table must be contiguous fp32 [N, 4, 32]")
-        lib = L.load()
-        qn = torch.empty_like(qkv) if keep_raw else qkv          # in place when no backward will ask for the raw projections
-        L.check(lib.tv_qknorm_rope_fwd(ops._p(qkv), ops._p(wq), ops._p(wk), ops._p(rope_tab), ops._p(qn), B, N, heads, eps, ops._stream()),
-                "tv_qknorm_rope_fwd")
-        o = torch.empty((B, N, heads * 64), dtype=torch.bfloat16, device=qkv.device)
-        lse = torch.empty((B, heads, N), dtype=torch.float32, device=qkv.device)
-        L.check(lib.tv_attn_fwd(ops._p(qn), ops._p(o), ops._p(lse), B, N, heads, scale, ops._stream()), "tv_attn_fwd")
-        ctx.args = (heads, scale, eps)
-        if keep_raw:
-            ctx.save_for_backward(qkv, qn, o, lse, wq, wk, rope_tab)
-        return o
-
-    @staticmethod
-    def backward(ctx, go):
-        qkv, qn, o, lse, wq, wk, rope_tab = ctx.saved_tensors
-        heads, scale, eps = ctx.args
-        B, N, _ = qkv.shape
-        lib = L.load()
-        go = go.contiguous()
-        ops._require(go.dtype == torch.bfloat16, "qk_norm_rope_attention: bf16 gradient rows")
-        delta = torch.empty((2, B, heads, N), dtype=torch.float32, device=qkv.device)   # scratch: -delta, -lse log2(e)
-        dqkv = torch.empty_like(qkv)
-        # with the table tv_attn_bwd stores dq / dk with respect to the un-rotated operands: the norm's backward has no rotation in it
-        L.check(lib.tv_attn_bwd(ops._p(qn), ops._p(o), ops._p(go), ops._p(lse), ops._p(delta), ops._p(rope_tab), ops._p(dqkv), B, N, heads, scale,
-                                ops._stream()), "tv_attn_bwd")
-        dwq, dwk = torch.empty_like(wq), torch.empty_like(wk)
-        part = torch.empty(lib.tv_qknorm_rope_bwd_partial_count(B, N, heads), dtype=torch.float32, device=qkv.device)
-        L.check(lib.tv_qknorm_rope_bwd(ops._p(qkv), ops._p(wq), ops._p(wk), ops._p(dqkv), ops._p(dwq), ops._p(dwk), ops._p(part), B, N, heads, eps,
-                                       ops._stream()), "tv_qknorm_rope_bwd")
-        return dqkv, dwq, dwk, None, None, None, None, None
-
-
-class _QkNormRopeAttnHdFn(torch.autograd.Function):
-    """`_QkNormRopeAttnFn` at head_dim 72: the tv_*_hd entries of csrc/attention_hd.hip, weights [72], table [N, 4, 36]."""
+    """Per-head RMSNorm of q and k, RoPE and attention at head_dim 64 or 72: weights [head_dim], table [N, 4, head_dim // 2]."""
 
     @staticmethod
     def forward(ctx, qkv, wq, wk, rope_tab, heads, scale, eps, keep_raw, hd):
-        ops._need_gpu(qkv)
-        ops._require(qkv.dtype == torch.bfloat16 and qkv.is_contiguous() and qkv.dim() == 3, "qk_norm_rope_attention: contiguous bf16 qkv [B, N, 3 C]")
-        B, N, C3 = qkv.shape
-        ops._require(C3 == 3 * heads * hd, f"qk_norm_rope_attention: the last axis must be 3 * heads * head_dim (head_dim = {hd})")
+        ops.check_qkv(qkv, rope_tab, heads, hd, "qk_norm_rope_attention")
+        B, N, _ = qkv.shape
         _check_weight(wq, hd, qkv, "qk_norm_rope_attention: q_norm")
         _check_weight(wk, hd, qkv, "qk_norm_rope_attention: k_norm")
-        if rope_tab is not None:
-            ops._require(rope_tab.dtype == torch.float32 and tuple(rope_tab.shape) == (N, 4, hd // 2) and rope_tab.is_contiguous() and
-                         rope_tab.device == qkv.device, f"qk_norm_rope_attention: the RoPE table must be contiguous fp32 [N, 4, {hd // 2}]")
-        lib = L.load()
         qn = torch.empty_like(qkv) if keep_raw else qkv          # in place when no backward will ask for the raw projections
-        L.check(lib.tv_qknorm_rope_fwd_hd(ops._p(qkv), ops._p(wq), ops._p(wk), ops._p(rope_tab), ops._p(qn), B, N, heads, hd, eps, ops._stream()),
-                "tv_qknorm_rope_fwd_hd")
+        ops.hd_call("tv_qknorm_rope_fwd", hd, (ops._p(qkv), ops._p(wq), ops._p(wk), ops._p(rope_tab), ops._p(qn)), B, N, heads, eps)
         o = torch.empty((B, N, heads * hd), dtype=torch.bfloat16, device=qkv.device)
         lse = torch.empty((B, heads, N), dtype=torch.float32, device=qkv.device)
-        L.check(lib.tv_attn_fwd_hd(ops._p(qn), ops._p(o), ops._p(lse), B, N, heads, hd, scale, ops._stream()), "tv_attn_fwd_hd")
+        ops.hd_call("tv_attn_fwd", hd, (ops._p(qn), ops._p(o), ops._p(lse)), B, N, heads, scale)
         ctx.args = (heads, scale, eps, hd)
         if keep_raw:
             ctx.save_for_backward(qkv, qn, o, lse, wq, wk, rope_tab)
@@ -118,12 +67,14 @@ class _QkNormRopeAttnHdFn(torch.autograd.Function):
         ops._require(go.dtype == torch.bfloat16, "qk_norm_rope_attention: bf16 gradient rows")
         delta = torch.empty((2, B, heads, N), dtype=torch.float32, device=qkv.device)   # scratch: -delta, -lse log2(e)
         dqkv = torch.empty_like(qkv)
-        L.check(lib.tv_attn_bwd_hd(ops._p(qn), ops._p(o), ops._p(go), ops._p(lse), ops._p(delta), ops._p(rope_tab), ops._p(dqkv), B, N, heads, hd,
-                                   scale, ops._stream()), "tv_attn_bwd_hd")
+        # with the table tv_attn_bwd stores dq / dk with respect to the un-rotated operands: the norm's backward has no rotation in it
+        ops.hd_call("tv_attn_bwd", hd, (ops._p(qn), ops._p(o), ops._p(go), ops._p(lse), ops._p(delta), ops._p(rope_tab), ops._p(dqkv)),
+                    B, N, heads, scale)
         dwq, dwk = torch.empty_like(wq), torch.empty_like(wk)
-        part = torch.empty(lib.tv_qknorm_rope_bwd_hd_partial_count(B, N, heads, hd), dtype=torch.float32, device=qkv.device)
-        L.check(lib.tv_qknorm_rope_bwd_hd(ops._p(qkv), ops._p(wq), ops._p(wk), ops._p(dqkv), ops._p(dwq), ops._p(dwk), ops._p(part), B, N, heads, hd,
-                                          eps, ops._stream()), "tv_qknorm_rope_bwd_hd")
+        count = lib.tv_qknorm_rope_bwd_partial_count(B, N, heads) if hd == 64 else lib.tv_qknorm_rope_bwd_hd_partial_count(B, N, heads, hd)
+        part = torch.empty(count, dtype=torch.float32, device=qkv.device)
+        ops.hd_call("tv_qknorm_rope_bwd", hd, (ops._p(qkv), ops._p(wq), ops._p(wk), ops._p(dqkv), ops._p(dwq), ops._p(dwk), ops._p(part)),
+                    B, N, heads, eps)
         return dqkv, dwq, dwk, None, None, None, None, None, None
 
 
@@ -166,10 +117,7 @@ def qk_norm_rope_attention(qkv: torch.Tensor, q_weight: torch.Tensor, k_weight: 
     one) the norm and the rotation run IN PLACE on `qkv`, which the caller must not reuse; otherwise the raw projections are kept
     for the backward.  `head_dim` is 64 or 72 (never inferred from the shapes); 72 takes a table [N, 4, 36]."""
     keep_raw = torch.is_grad_enabled() and (qkv.requires_grad or q_weight.requires_grad or k_weight.requires_grad)
-    if head_dim == 64:
-        return _QkNormRopeAttnFn.apply(qkv, q_weight, k_weight, rope_tab, int(heads), float(scale), float(eps), bool(keep_raw))
-    ops._require(head_dim == 72, f"qk_norm_rope_attention: head_dim={head_dim} must be 64 or 72")
-    return _QkNormRopeAttnHdFn.apply(qkv, q_weight, k_weight, rope_tab, int(heads), float(scale), float(eps), bool(keep_raw), 72)
+    return _QkNormRopeAttnFn.apply(qkv, q_weight, k_weight, rope_tab, int(heads), float(scale), float(eps), bool(keep_raw), int(head_dim))
 
 
 def swiglu(u: torch.Tensor) -> torch.Tensor:

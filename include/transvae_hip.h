@@ -664,7 +664,7 @@ int tv_flow_loss_cos(const void* pred, const float* lat, long long sn, long long
 int tv_flow_heun(float* x, const void* v1, const void* v2, int B, int D, int h, int w, int patch, int ld, float dt, float cfg_scale, int guided1,
                  int guided2, void* stream);
 
-/* LightningDiT block variants: RMSNorm adaLN, per-head qk-norm with RoPE, SwiGLU (csrc/lightning.hip) -----------------------------------
+/* LightningDiT block variants: RMSNorm adaLN (csrc/dit.hip), per-head qk-norm with RoPE (csrc/qk_norm.hip), SwiGLU (csrc/lightning.hip) ---
  * The conventions of the DiT block above: bf16 token matrices [B N, C], 16-byte aligned, C % 8 == 0; the fp32 [B, ld] modulation
  * matrix read by column offsets; every sum that crosses rows goes through scratch partials in a fixed order and is WRITTEN (no
  * accumulation, no atomics anywhere in the file: the same bits on every run).  Rounding contract: DESIGN.md section 3.1 row J;
@@ -681,8 +681,8 @@ int tv_adaln_rms_fwd(const void* x, const float* w, const float* mod, int shift_
 long long tv_adaln_rms_bwd_partial_count(int B, int N, int C);
 int tv_adaln_rms_bwd(const void* x, const float* w, const float* mod, int shift_off, int scale_off, int ld, const void* dy, const void* dres, void* dx,
                      float* dmod, float* dw, float* partials, int B, int N, int C, float eps, void* stream);
-/* Per-head RMSNorm of q and k, then the RoPE of tv_rope_qk, on qkv [B, N, 3, heads, 64] bf16; wq, wk fp32 [64]; rope_tab [N, 4, 32]
- * fp32 or NULL (no rotation).
+/* Per-head RMSNorm of q and k, then the RoPE of tv_rope_qk (csrc/qk_norm.hip, the <64> kernels), on qkv [B, N, 3, heads, 64] bf16;
+ * wq, wk fp32 [64]; rope_tab [N, 4, 32] fp32 or NULL (no rotation).
  * tv_qknorm_rope_fwd: per (token, head), q and k alike: r = rsqrt(mean_64(q^2) + eps) (eight lanes of 16 bytes, a three-step
  * butterfly), z = (q r) w, rotated in fp32 (two products and their sum per output, as tv_rope_qk), rounded to bf16 once; the v third
  * is copied bit for bit.  out may be qkv itself (each 64-vector is read whole before it is written) or must not overlap it.
@@ -702,7 +702,8 @@ int tv_qknorm_rope_bwd(const void* qkv, const float* wq, const float* wk, void* 
 int tv_swiglu_fwd(const void* u, void* h, long long T, int Hp, void* stream);
 int tv_swiglu_bwd(const void* u, const void* dh, void* du, long long T, int Hp, void* stream);
 
-/* The head_dim 72 family (csrc/attention_hd.hip; DiT-XL / LightningDiT-XL: 1152 = 16 heads of 72) --------------------------------------
+/* The head_dim 72 family (csrc/attention_hd.hip; the qk-norm pair is csrc/qk_norm.hip, one template over head_dim with the entries
+ * above; DiT-XL / LightningDiT-XL: 1152 = 16 heads of 72) -----------------------------------------------------------------------------
  * The entries above at another head dimension: the same argument lists plus `head_dim`, which must be 72 here (any other value
  * returns TV_ERR_ARG with an error text naming head_dim; 64 has the entries above).  Heads sit at their natural stride, nothing in
  * HBM is padded: qkv [B, N, 3, heads, 72] bf16 (a head vector is 144 bytes = nine 16-byte pieces), o [B, N, heads, 72] bf16, lse

@@ -1,4 +1,5 @@
-"""Launch transcripts of the op layer (transvae/hip/ops.py, fused.py), recorded on the CPU.
+"""Launch transcripts of the op layer (transvae/hip/ops.py, fused.py, and the qk-norm attention of transvae/lightning_dit.py),
+recorded on the CPU.
 
 The library is replaced by a recorder: every entry point appends (name, arguments) to a list and returns 0, so the whole
 op layer -- descriptors, chunking, caches, in-place accumulation -- runs on CPU tensors and what it WOULD launch can be
@@ -199,6 +200,32 @@ def case_attn(rec, ops, fused):
                                             par(rec, "wp", C_, C_), par(rec, "bp", C_), tab, B, N, 1, 0.125, 1e-6, 1e-5))
 
 
+def _attention(hd, table):
+    """ops.attention forward and backward on qkv [2, 16, 3 * hd] (one head)."""
+    def run(rec, ops, fused):
+        B, N = 2, 16
+        qkv = act(rec, "qkv", B, N, 3 * hd, grad=True)
+        tab = rec.label("tab", torch.zeros((N, 4, hd // 2))) if table else None
+        _zero_backward(ops.attention(qkv, tab, 1, 0.125, head_dim=hd))
+    return run
+
+
+def _qk_norm_attention(hd, grad):
+    """lightning_dit.qk_norm_rope_attention with a table: raw projections kept and the backward run, or in place under no_grad."""
+    def run(rec, ops, fused):
+        from transvae import lightning_dit
+        B, N = 2, 16
+        qkv = act(rec, "qkv", B, N, 3 * hd, grad=grad)
+        wq, wk = par(rec, "wq", hd), par(rec, "wk", hd)
+        tab = rec.label("tab", torch.zeros((N, 4, hd // 2)))
+        if grad:
+            _zero_backward(lightning_dit.qk_norm_rope_attention(qkv, wq, wk, tab, 1, 0.125, 1e-6, head_dim=hd))
+        else:
+            with torch.no_grad():
+                lightning_dit.qk_norm_rope_attention(qkv, wq, wk, tab, 1, 0.125, 1e-6, head_dim=hd)
+    return run
+
+
 def _ffn_args(rec, with_grad=False, freeze=False):
     d, hid, mid = 64, 256, 64
     p = lambda n, *s, grad=True: par(rec, n, *s, grad=grad, with_grad=with_grad and grad)   # noqa: E731
@@ -287,6 +314,9 @@ def _cases():
         "up": _up(False), "up_dc": _up(True), "up_dc_in_place": _up(True, True),
         "chunk_resblock": _resblock(chunk=True), "chunk_rope": case_chunk_rope, "chunk_wgrad": case_chunk_wgrad,
     })
+    for hd in (64, 72):
+        cases.update({f"attention_hd{hd}": _attention(hd, False), f"attention_hd{hd}_rope": _attention(hd, True),
+                      f"qk_norm_attention_hd{hd}": _qk_norm_attention(hd, True), f"qk_norm_attention_hd{hd}_no_grad": _qk_norm_attention(hd, False)})
     return cases
 
 

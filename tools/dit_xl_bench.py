@@ -1,4 +1,4 @@
-"""Cost of the head_dim 72 kernels (csrc/attention_hd.hip) and of the XL models (transvae.dit_xl / lightning_dit_xl).  GPU box.
+"""Cost of the head_dim 72 kernels (csrc/attention_hd.hip, and the <72> instantiations of csrc/qk_norm.hip) and of the XL models (transvae.dit_xl / lightning_dit_xl).  GPU box.
 
     python tools/dit_xl_bench.py [--iters 5] [--out profiles/dit_xl_bench.json]
 
@@ -37,9 +37,9 @@ B, N, C_, D, HW, P, DEPTH = 256, 256, 1152, 32, 16, 1, 28
 GEOM = {72: 16, 64: 18}                       # head_dim -> heads at width 1152
 FLOPS = 4 * B * N * N * C_                    # one pass of q k^T and P v (the backward: 2.5 x by the formulas, 3.5 x as split here)
 KERNELS = ("attn72_fwd_kernel", "attn72_delta_kernel", "attn72_bwd_dq_kernel", "attn72_bwd_dkv_kernel", "rope_qk72_kernel",
-           "qknorm72_rope_fwd_kernel", "qknorm72_rope_bwd_kernel", "qknorm72_finalize_kernel",
+           "qknorm_rope_fwd_kernel<72>", "qknorm_rope_bwd_kernel<72>", "qknorm_finalize_kernel<72>",
            "attn_fwd_kernel", "attn_delta_kernel", "attn_bwd_dq_kernel", "attn_bwd_dkv_kernel", "rope_qk_kernel",
-           "qknorm_rope_fwd_kernel", "qknorm_rope_bwd_kernel", "qknorm_finalize_kernel")
+           "qknorm_rope_fwd_kernel<64>", "qknorm_rope_bwd_kernel<64>", "qknorm_finalize_kernel<64>")
 PAIRS = ("attn_fwd", "attn_bwd", "rope_qk", "qknorm_rope_fwd", "qknorm_rope_bwd")
 
 
@@ -210,15 +210,22 @@ def child_trace(a):
     torch.cuda.synchronize()
 
 
+def is_kernel(k, name):
+    """Whether a rocprofv3 kernel name is kernel k of KERNELS.  Names come demangled or, for some, mangled; the qk-norm kernels are
+    one template over head_dim, `kernel<72>` demangled and `kernelILi72EE` mangled."""
+    base, _, arg = k.partition("<")
+    return f"::{k}(" in name or f"{len(base)}{base}" + (f"ILi{arg[:-1]}EE" if arg else "E") in name
+
+
 def kernel_table(path):
-    """kernel -> average time and calls out of a rocprofv3 kernel_stats.csv (names come demangled or, for some, mangled)"""
+    """kernel -> average time and calls out of a rocprofv3 kernel_stats.csv"""
     with open(path) as f:
         table = list(csv.DictReader(f))
     out = {}
     for row in table:
         name, avg_ns = row.get("Name", ""), float(row.get("AverageNs") or 0)
         for k in KERNELS:
-            if f"::{k}(" in name or f"{len(k)}{k}E" in name:
+            if is_kernel(k, name):
                 out[k] = {"avg_us": round(avg_ns / 1e3, 2), "calls": int(row.get("Calls") or 0)}
     return out
 

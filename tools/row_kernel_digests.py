@@ -1,5 +1,6 @@
 """SHA-256 digests of what the wave-per-row kernels write (csrc/row_wave.h: the row norms of csrc/norm.hip, the adaLN pairs of
-csrc/dit.hip), for proving that a change to them moved no bit.  GPU box.
+csrc/dit.hip) and of what the per-head qk-norm kernels write (csrc/qk_norm.hip, head_dim 64 and 72), for proving that a change
+to them moved no bit.  GPU box.
 
     python tools/row_kernel_digests.py --out new.json                      # the in-tree library
     TV_HIP_SO=/path/to/other.so python tools/row_kernel_digests.py --out old.json
@@ -11,6 +12,9 @@ filled last chunks and completely filled lanes -- times (B, N) in {(2, 1), (3, 6
 whole slabs.  Rows sit 8 standard deviations from 0, so that the centring matters.  The `dw` of tv_rownorm_bwd mode 1 is summed by
 atomics in no fixed order: it is kept as values, not hashed, and --compare prints its largest
 difference relative to the tensor's largest entry, which is order noise of about 1e-7.
+The qk-norm pair at both head dims: forward out of place and in place, with and without a table (arbitrary fp32 [N, 4, hd / 2]);
+backward: dqkv, dwq and dwk, all hashed (fixed-order sums).  (B, N, heads) in QK: a ragged last group, one-token samples, a short
+slab, more than one backward pass per block (36864 head vectors against 1024 blocks of 32 or 16), more than one forward pass.
 """
 import argparse
 import base64
@@ -26,6 +30,7 @@ sys.path.insert(0, os.path.join(ROOT, "deepl-project_amd"))
 CS_ADALN = (8, 128, 384, 768, 1152, 1536)
 CS_NORM = CS_ADALN + (2560,)
 BN = ((2, 1), (3, 65), (2, 256))
+QK = ((1, 5, 3), (2, 1, 6), (3, 65, 2), (3, 256, 24), (1, 16500, 1))
 EPS = 1e-6
 
 
@@ -102,6 +107,26 @@ def digests():
             call("tv_gate_residual_bwd", p(dy), p(x), p(mod), gate_off, ld, p(dyg), p(dmod), p(part), B, N, Cc)
             sha(f"tv_gate_residual_bwd {tag}: dy", dyg)
             sha(f"tv_gate_residual_bwd {tag}: dgate", dmod[:, gate_off:gate_off + Cc])
+
+    for hd in (64, 72):
+        s, h = ("", ()) if hd == 64 else ("_hd", (hd,))
+        for B, N, heads in QK:
+            g = torch.Generator().manual_seed(100 * hd + B + N + heads)
+            qkv, dq = (torch.randn(B, N, 3 * heads * hd, generator=g).bfloat16().to(dev) for _ in range(2))
+            wq, wk = ((1 + 0.1 * torch.randn(hd, generator=g)).to(dev) for _ in range(2))
+            tab = torch.randn(N, 4, hd // 2, generator=g).to(dev)
+            tag = f"hd={hd} B={B} N={N} heads={heads}"
+            for t in (None, tab):
+                y, z = torch.full_like(qkv, 7.0), qkv.clone()
+                call(f"tv_qknorm_rope_fwd{s}", p(qkv), p(wq), p(wk), p(t), p(y), B, N, heads, *h, EPS)
+                sha(f"tv_qknorm_rope_fwd{s} table={int(t is not None)} {tag}: out", y)
+                call(f"tv_qknorm_rope_fwd{s}", p(z), p(wq), p(wk), p(t), p(z), B, N, heads, *h, EPS)
+                sha(f"tv_qknorm_rope_fwd{s} table={int(t is not None)} in place {tag}: out", z)
+            dqkv, dwq, dwk = dq.clone(), torch.full((hd,), 7.0, device=dev), torch.full((hd,), 7.0, device=dev)
+            part = torch.empty(getattr(lib, f"tv_qknorm_rope_bwd{s}_partial_count")(B, N, heads, *h), device=dev)
+            call(f"tv_qknorm_rope_bwd{s}", p(qkv), p(wq), p(wk), p(dqkv), p(dwq), p(dwk), p(part), B, N, heads, *h, EPS)
+            for nm, t in (("dqkv", dqkv), ("dwq", dwq), ("dwk", dwk)):
+                sha(f"tv_qknorm_rope_bwd{s} {tag}: {nm}", t)
     return {"library": L.SO_PATH, "sha256": out, "values": values}
 
 
